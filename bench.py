@@ -7,6 +7,10 @@ throw-away session, then a fresh session is prefilled with the 129-row prompt (1
 AbstractModel.java:549-555) and EXACTLY K greedy decode steps are timed (clock starts after the first sampled
 token, AbstractModel.java:589), bracketed by barrier + device synchronize; rank 0 prints ONE JSON line.
 
+`--dump-outputs DIR` (N=1): after the timed steps, what the timed path behind `value` handed its caller is written as
+DIR/tokens.npy (the K greedy ids, float64) and DIR/logits.npy (the logits of the last timed step, float32 [V]).  Weights and
+prompt are seeded, so two builds run with the same arguments can be compared output for output.
+
 N=1: the whole model on one GPU.  N>1: DistributedContext layer split (DistributedContext.java:75-77) -- rank r owns
 layers [r*L/N,(r+1)*L/N) and its KV pages; [1,E] F32 activations hop rank->rank with RCCL send/recv and the sampled
 token returns to rank 0 (jlama_amd/distributed.py).
@@ -106,7 +110,23 @@ def parse():
     ap.add_argument("--probe-iters", type=int, default=3)
     ap.add_argument("--no-tier1-host", action="store_true")   # skip the host-as-is leg (tier1_host_tokens_per_s)
     ap.add_argument("--tier1-steps", type=int, default=8)     # decode steps of that leg (each ~0.1-0.3 s on the 8B model)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None)   # write the timed path's outputs as DIR/<name>.npy (N=1 only)
     return ap.parse_args()
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """Write {name: array} as dirname/<name>.npy: integer arrays as float64 (exact for token ids), float arrays as float32."""
+    conv = {k: np.ascontiguousarray(v, dtype=np.float64 if np.issubdtype(np.asarray(v).dtype, np.integer) else np.float32)
+            for k, v in arrays.items()}
+    total = sum(a.nbytes for a in conv.values())
+    assert total <= DUMP_MAX_BYTES, f"outputs to dump are {total} bytes, more than {DUMP_MAX_BYTES}"
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in conv.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+    return sorted(conv)
 
 
 TF_STEPS = 32
@@ -320,6 +340,8 @@ def run_single(args, cfg):
     t_w = time.perf_counter()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    # logits of the last timed step, read before the probes below reuse the session (outside the bracket)
+    fast_outputs = {"tokens": toks, "logits": s.logits()} if args.dump_outputs else None
     if os.environ.get("JH_BENCH_DEBUG"):
         print(f"[bench] queue {1e3 * (t_a - t0):.2f} ms, wait {1e3 * (t_w - t_a):.2f} ms, torch sync {1e3 * (t0 + dt - t_w):.2f} ms", file=sys.stderr)
     assert toks.size == args.steps
@@ -338,6 +360,7 @@ def run_single(args, cfg):
     # ---- the same K steps in REFERENCE ORDER (jh_p16.h: every float accumulation in the Panama provider's order; ids and logits
     # bit-identical to the oracle, see parity_full_size): timed exactly like `value`, in this same process
     strict = None
+    strict_outputs = None
     if not args.no_strict:
         ss = model.session(max_ctx)
         ss.set_strict(True)                    # the whole leg in reference order: prompt (M-row p16 GEMMs), sampling, decode
@@ -357,6 +380,7 @@ def run_single(args, cfg):
         torch.cuda.synchronize()
         sdt = time.perf_counter() - t0
         assert stoks.size == args.steps
+        strict_outputs = {"tokens": stoks, "logits": ss.logits()} if args.dump_outputs else None   # before the metric-shape run reuses ss
         sev_ms, skernels = ss.decode_stats()
         # the metric's own shape (BASELINE: 256 decode steps behind the 129-row prompt) whatever K the caller asked for: the same
         # session, the same bracket, positions prompt.size ... prompt.size + 255 -- the driver's K = 20 covers positions 129..148 only
@@ -507,6 +531,10 @@ def run_single(args, cfg):
         ids_ref = ids_o if (not args.no_parity and is_q4) else None
         out["tier1_host"] = tier1_host_leg(cfg, host_w, prompt, args.tier1_steps, ids_ref)
         out["tier1_host_tokens_per_s"] = out["tier1_host"]["tokens_per_s"]
+    if args.dump_outputs:
+        headline_strict = strict_outputs is not None and not args.fast_order   # the leg whose rate is `value`
+        names = dump_outputs(args.dump_outputs, strict_outputs if headline_strict else fast_outputs)
+        out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": names, "order": "reference" if headline_strict else "order-free"}
     return out, toks
 
 
@@ -604,6 +632,8 @@ def main():
     from jlama_amd import synthetic as S
     cfg = dict(getattr(S, args.config))
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.dump_outputs and (args.gpus > 1 or world > 1 or os.environ.get("JH_BENCH_FORCE_PIPELINE")):
+        sys.exit("bench.py: --dump-outputs is implemented for the one-GPU line only")
     if "RANK" in os.environ and world > 1:
         # one rank per GPU under torch.distributed.run: the RCCL send/recv pipeline
         from jlama_amd import distributed as D

@@ -1075,7 +1075,6 @@ def bench_pipeline(args, cfg, backend="nccl", engine_factory=None, tp_engine_fac
 if __name__ == "__main__":
     import argparse
     import json
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")   # only matters when several shards share one device (loopback runs)
     ap = argparse.ArgumentParser()
     ap.add_argument("--one-process", action="store_true")
     ap.add_argument("--tp-ipc-selftest", action="store_true")

@@ -5,9 +5,8 @@ import pytest
 
 # The tensor-parallel loopback tests run several shards' streams side by side on ONE device, kernels of one stream waiting for
 # kernels of another: each stream needs its own hardware queue.  The one-process group makes sure of that itself (CU-masked
-# streams, jh_tp_group_create); the raised queue count keeps the other multi-stream tests (pipeline stages, concurrent sessions)
-# off shared queues.  Read when HIP initialises, so it is set before anything imports torch.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+# streams, jh_tp_group_create); rank-per-process groups have a process, and so queues, per shard.  The process's hardware
+# queue count is left as the environment sets it.
 
 try:   # torch bundles its own HIP runtime: when a test mixes torch.cuda with libjlamahip.so, torch must be loaded first
     import torch  # noqa: F401

@@ -1083,7 +1083,7 @@ def test_rank_per_process_tensor_parallel_over_ipc(gpu, oracle, strict):
     n_gen = 12
     sk = socket.socket(); sk.bind(("127.0.0.1", 0)); port = sk.getsockname()[1]; sk.close()
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, GPU_MAX_HW_QUEUES="8", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     procs = [subprocess.Popen([sys.executable, "-m", "jlama_amd.distributed", "--tp-ipc-selftest", "--rank", str(r), "--world", "2", "--port", str(port),
                                "--n-gen", str(n_gen), "--strict", str(strict)], cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
              for r in range(2)]
@@ -1122,7 +1122,7 @@ def test_bench_tensor_parallel_leg_rank_per_process(gpu):
     n_gen = 12
     sk = socket.socket(); sk.bind(("127.0.0.1", 0)); port = sk.getsockname()[1]; sk.close()
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, GPU_MAX_HW_QUEUES="8", HSA_ENABLE_IPC_MODE_LEGACY="0", JH_TP_SELFTEST_BENCH="1")
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", JH_TP_SELFTEST_BENCH="1")
     procs = [subprocess.Popen([sys.executable, "-m", "jlama_amd.distributed", "--tp-ipc-selftest", "--rank", str(r), "--world", "2", "--port", str(port),
                                "--n-gen", str(n_gen), "--strict", "1"], cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
              for r in range(2)]

@@ -41,7 +41,7 @@ def test_decode_timeline_tool_on_a_synthetic_trace(tmp_path):
     assert "| gemv_i8q4_kernel<1, 2, 2, 2, 1> | 2 | 15.00 | 0.50 |" in out
 
 
-def test_reference_order_streaming_loops_do_not_copy_their_prefetch_ring():
+def test_reference_order_streaming_loops_do_not_copy_their_prefetch_ring(tmp_path):
     """tools/isa_ring_copies.py on the two units that hold the reference-order streaming GEMVs: no loop may end with a block of
     register moves behind s_waitcnt vmcnt(...) -- the shape hipcc gives a prefetch ring whose refills land in fresh registers, which
     makes every ring block wait out a full memory round trip (what bounded the few-row GEMVs until round 5)."""
@@ -54,20 +54,20 @@ def test_reference_order_streaming_loops_do_not_copy_their_prefetch_ring():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     tool = os.path.join(root, "tools", "isa_ring_copies.py")
     for unit in ("gemv_ref", "gemv_bf16"):
-        r = subprocess.run([sys.executable, tool, unit], capture_output=True, text=True, timeout=900)
+        r = subprocess.run([sys.executable, tool, unit, "--out", str(tmp_path / f"_isa_{unit}.s")], capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr
         assert f"{unit}: no loop ends by copying a prefetch ring" in r.stdout, r.stdout[:2000]
-    # the same ISA (isa_ring_copies.py leaves it in /tmp/_isa_<unit>.s): no register with a pending asm-issued LDS write is touched,
+    # the same ISA (isa_ring_copies.py leaves it in <tmp_path>/_isa_<unit>.s): no register with a pending asm-issued LDS write is touched,
     # and none is pending at a label or a branch (tools/isa_pending_lds.py; the few-row GEMVs hold their activation operands that way)
     pend = os.path.join(root, "tools", "isa_pending_lds.py")
-    r = subprocess.run([sys.executable, pend, "--file", "/tmp/_isa_gemv_ref.s"], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, pend, "--file", str(tmp_path / "_isa_gemv_ref.s")], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "no register touched while its LDS write is pending" in r.stdout, r.stdout[-3000:]
     assert " 0 asm LDS reads" not in r.stdout, "the checker found no hand-pipelined read at all: " + r.stdout
     # and no streaming kernel drains its prefetch ring in front of the prologue barrier (tools/isa_ring_drain.py: a wait for fewer
     # loads than the ring holds between the fill and the barrier -- round 6: one register collision cost the o-projection 12 %)
     drain = os.path.join(root, "tools", "isa_ring_drain.py")
     for unit in ("gemv_ref", "gemv_bf16"):
-        r = subprocess.run([sys.executable, drain, "--file", f"/tmp/_isa_{unit}.s"], capture_output=True, text=True, timeout=900)
+        r = subprocess.run([sys.executable, drain, "--file", str(tmp_path / f"_isa_{unit}.s")], capture_output=True, text=True, timeout=900)
         assert r.returncode == 0 and ", 0 drain their ring" in r.stdout, r.stdout[-3000:]
         assert " 0 streaming kernels checked" not in r.stdout
 

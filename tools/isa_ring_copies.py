@@ -2,13 +2,19 @@
 """Scan the gfx950 ISA of one translation unit for loops that end by COPYING registers behind s_waitcnt vmcnt(...): the sign of a
 prefetch ring whose refills landed in fresh registers (hipcc then closes the loop by moving the ring back, waiting for the
 youngest load each time round -- what made the reference-order few-row GEMVs latency-bound until round 5).
-usage: isa_ring_copies.py <unit, e.g. gemv_ref> [min copies = 4]"""
+usage: isa_ring_copies.py <unit, e.g. gemv_ref> [min copies = 4] [--out <asm file> (default /tmp/_isa_<unit>.s)]"""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-unit = sys.argv[1] if len(sys.argv) > 1 else "gemv_ref"
-mincp = int(sys.argv[2]) if len(sys.argv) > 2 else 4
+argv = sys.argv[1:]
+out = None
+if "--out" in argv:
+    i = argv.index("--out")
+    out = argv[i + 1]
+    del argv[i:i + 2]
+unit = argv[0] if len(argv) > 0 else "gemv_ref"
+mincp = int(argv[1]) if len(argv) > 1 else 4
 src = os.path.join(ROOT, "jlama_amd", "csrc", unit + ".hip")
-asm = f"/tmp/_isa_{unit}.s"
+asm = out or f"/tmp/_isa_{unit}.s"
 subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden", "-Wno-unused-value",
                 "-S", "--offload-device-only", src, "-o", asm], check=True, capture_output=True)
 fn, block, found = None, [], {}

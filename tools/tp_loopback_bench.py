@@ -1,9 +1,8 @@
 """Single-stream decode rate of the one-process tensor-parallel group (jh_tp_group_*) with all head-split shards on ONE device
 against the un-sharded model: graph-replayed shards that meet in kernels (default) and the event-ordered host loop (JH_TP_GRAPH=0).
 All shards on one device need one HARDWARE queue per shard stream (a spinning kernel blocks a queue it shares with the kernel it
-waits for): GPU_MAX_HW_QUEUES is raised before HIP initialises; with one shard per device this does not arise."""
+waits for): the group gives same-device shards CU-masked streams, a queue each; with one shard per device this does not arise."""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from jlama_amd import _native as N, distributed as D, synthetic as S
