@@ -1,4 +1,5 @@
 """Loader / builder of libjlamahip.so and its ctypes prototypes (include/jlama_hip.h)."""
+import contextlib
 import ctypes as C
 import hashlib
 import os
@@ -73,25 +74,31 @@ def _unit_key(unit, hdr_digest):
     return h.hexdigest()[:32]
 
 
-def build(force=False, verbose=False, jobs=None):
-    """Compile libjlamahip.so for gfx950 (hipcc cross-compiles without a GPU): one object per translation unit, in parallel,
-    then one link.  Without `force` the whole step is skipped only when the existing binary carries the hash of the current
-    sources, and an object is reused only when ITS source, every header and the flags hash to the key stored beside it
-    (never by timestamps).  `force` recompiles every unit."""
+@contextlib.contextmanager
+def _build_lock():
+    """Several ranks of one torchrun may get here at once: one builds, the others wait and find the fresh binaries."""
     import fcntl
     os.makedirs(OBJ_DIR, exist_ok=True)
-    want = source_hash()
-    if not force and built_hash() == want:
-        return LIB_PATH
-    # several ranks of one torchrun may get here at once: one builds, the others wait and find the fresh binary
     with open(os.path.join(os.path.dirname(LIB_PATH), ".build.lock"), "w") as lockf:
         fcntl.flock(lockf, fcntl.LOCK_EX)
         try:
-            if not force and built_hash() == want:
-                return LIB_PATH
-            return _build_locked(want, force, verbose, jobs)
+            yield
         finally:
             fcntl.flock(lockf, fcntl.LOCK_UN)
+
+
+def build(force=False, verbose=False, jobs=None):
+    """Compile libjlamahip.so for gfx950 (hipcc cross-compiles without a GPU): one object per translation unit, in parallel,
+    then one link, then libjlamahost.so.  Without `force` the device library is skipped only when the existing binary carries
+    the hash of the current sources, and an object is reused only when ITS source, every header and the flags hash to the key
+    stored beside it (never by timestamps); the host library is checked against its own key either way.  `force` recompiles
+    every unit."""
+    want = source_hash()
+    with _build_lock():
+        if not force and built_hash() == want:
+            build_host(verbose=verbose)
+            return LIB_PATH
+        return _build_locked(want, force, verbose, jobs)
 
 
 def _build_locked(want, force, verbose, jobs):
@@ -151,11 +158,12 @@ def build_host(force=False, verbose=False):
     want = host_source_hash()
     if not force and os.path.exists(HOST_LIB_PATH) and os.path.exists(keyf) and open(keyf).read() == want:
         return HOST_LIB_PATH
-    cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-fopenmp", "-fvisibility=hidden", HOST_SRC, "-o", HOST_LIB_PATH,
+    cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-fopenmp", "-fvisibility=hidden", HOST_SRC, "-o", HOST_LIB_PATH + ".tmp",
            "-L" + os.path.dirname(LIB_PATH), "-ljlamahip", "-Wl,-rpath,$ORIGIN"]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
+    os.replace(HOST_LIB_PATH + ".tmp", HOST_LIB_PATH)   # a process that has the old one loaded keeps its mapping
     with open(keyf, "w") as f:
         f.write(want)
     return HOST_LIB_PATH
@@ -304,12 +312,13 @@ HOST_EXPORTS = sorted(_HOST_PROTOS)
 
 
 def host_lib():
-    """libjlamahost.so (csrc/host_mirror.cpp): the reference's host above the C ABI.  Loads libjlamahip.so first (its only dependency)."""
+    """libjlamahost.so (csrc/host_mirror.cpp): the reference's host above the C ABI.  Loads libjlamahip.so first (its only dependency),
+    and rebuilds libjlamahost.so first when it is missing or older than its source."""
     global _host_lib
     if _host_lib is None:
         lib()
-        if not os.path.exists(HOST_LIB_PATH):
-            raise RuntimeError(f"{HOST_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
+        with _build_lock():
+            build_host()
         L = C.CDLL(HOST_LIB_PATH)
         for name, (res, args) in _HOST_PROTOS.items():
             fn = getattr(L, name)

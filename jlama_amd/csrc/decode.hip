@@ -2,6 +2,26 @@
 #include "jh_host.h"
 #include "jh_launch.h"
 
+// ---- kernels of this unit: the decode-state setter and the embedding lookup of the current token (other units: the launchers below)
+namespace jh {
+
+static __global__ void set_state_kernel(DecodeState* st, int pos, int token, int step) {
+    st->pos = pos; st->token = token; st->step = step; st->done = 0;
+}
+static __global__ void embed_kernel(const void* table, const float* scales, int dtype, const DecodeState* st, int E,
+                             float* x) {
+    embed_row(table, scales, dtype, st->token, E, x);
+}
+
+}  // namespace jh
+
+void launch_set_state(DecodeState* d, int pos, int token, hipStream_t st) {
+    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, d, pos, token, 0);
+}
+void launch_embed(const JWeight& emb, const DecodeState* d, int E, float* x, hipStream_t st) {
+    hipLaunchKernelGGL(embed_kernel, dim3(1), dim3(256), 0, st, (const void*)emb.data, (const float*)emb.scales, emb.dtype, d, E, x);
+}
+
 // The RoPE row of kv head h at position p is table row p + 2*h (global head index): the reference's table has
 // context_length rows and Java throws ArrayIndexOutOfBoundsException beyond it -- same positions refused here.
 int check_positions(const jh_session* s, int last_pos) {
@@ -94,10 +114,9 @@ int forward_impl(jh_session* s, const int32_t* tokens, const float* x_in, bool x
         }
     }
     for (int i = done; i < n; i++) {
-        hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, s->st, start_pos + i, tokens ? tokens[i] : 0, 0);
+        launch_set_state(s->st, start_pos + i, tokens ? tokens[i] : 0, st);
         if (tokens) {
-            hipLaunchKernelGGL(embed_kernel, dim3(1), dim3(256), 0, st, (const void*)emb.data, (const float*)emb.scales, emb.dtype,
-                               (const DecodeState*)s->st, E, s->x);
+            launch_embed(emb, s->st, E, s->x, st);
         } else {
             HIPCHK(hipMemcpyAsync(s->x, x_in + (size_t)i * E, (size_t)E * 4, x_in_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
         }
@@ -146,7 +165,7 @@ int jh_sample(jh_session* s, float temperature, float u, int32_t* next_token, fl
     HIPCHK(hipSetDevice(s->m->device));
     hipStream_t st = s->stream;
     JHCHK(lmhead_launch(s, st));
-    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, s->st, 0, 0, 0);
+    launch_set_state(s->st, 0, 0, st);
     JHCHK(finish_launch(s, st, 0));
     int tok = 0;
     HIPCHK(hipMemcpyAsync(&tok, s->out_tokens, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -296,9 +315,8 @@ int decode_n_async_impl(jh_session* s, int32_t first_token, int start_pos, int n
         for (int v = 0; v < N_ATTN_VARIANTS; v++)
             if (attn_variant_in_range(s, v, start_pos, start_pos + n - 1)) JHCHK(build_graph(s, v, temperature));
     }
-    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, s->st, start_pos, first_token, 0);
-    hipLaunchKernelGGL(embed_kernel, dim3(1), dim3(256), 0, st, (const void*)emb.data, (const float*)emb.scales, emb.dtype,
-                       (const DecodeState*)s->st, m->c.embedding_length, s->x);
+    launch_set_state(s->st, start_pos, first_token, st);
+    launch_embed(emb, s->st, m->c.embedding_length, s->x, st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->ev0, st));
     // Stop tokens: the device freezes its state at the step that samples one (finish_token_kernel); the host keeps two

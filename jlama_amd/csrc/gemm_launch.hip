@@ -2,6 +2,32 @@
 #include "jh_host.h"
 #include "jh_launch.h"
 
+// ---- kernels of this unit: the split-K reduce of the MFMA GEMMs
+namespace jh {
+
+// second pass of a split-K GEMM: C[i][j] = sum_s ws[s][i][j] (ascending K ranges => deterministic) (+ resid)
+static __global__ void splitk_reduce_kernel(const float* ws, int nsplit, int m, int n, int n0, float* c, int ldc, int roffset, const float* resid) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)m * n) return;
+    const int row = (int)(i / n), col = (int)(i % n);
+    float v = 0.0f;
+    for (int s = 0; s < nsplit; s++) v += ws[(size_t)s * m * n + i];
+    const size_t idx = (size_t)ldc * row + (n0 + col) - roffset;
+    c[idx] = resid ? v + resid[idx] : v;
+}
+// the same sums, four columns per thread (n, ldc, n0 - roffset multiples of 4; 16-byte aligned buffers): grid (n/4 / 256, m)
+static __global__ __launch_bounds__(256) void splitk_reduce4_kernel(const f32x4* ws, int nsplit, int m, int n4, f32x4* c, int ldc4, int coff4, const f32x4* resid) {
+    const int col = blockIdx.x * 256 + threadIdx.x, row = blockIdx.y;
+    if (col >= n4) return;
+    const size_t i = (size_t)row * n4 + col, stride = (size_t)m * n4;
+    f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int s = 0; s < nsplit; s++) v = v + ws[s * stride + i];
+    const size_t idx = (size_t)ldc4 * row + coff4 + col;
+    c[idx] = resid ? v + resid[idx] : v;
+}
+
+}  // namespace jh
+
 template <int MT>
 int launch_gemm_q8q4_mfma_mt(const MfmaQ4Params& g, hipStream_t st) {
     const int tiles = g.n / 32;
@@ -46,7 +72,7 @@ int launch_splitk_reduce(const float* ws, int S, int m, int n, int n0, float* c,
     return JH_OK;
 }
 
-template <int CW, int CT, int S, bool PK = false>
+template <int CW, int CT, int S>
 int launch_gemm_q8q4_lds(const MfmaQ4Params& g, int mtiles, float* ws, size_t ws_bytes, hipStream_t st) {
     const int nblk = g.k / QB;
     const int cgroups = g.n / (32 * CW * CT), gg = (cgroups + 7) / 8;
@@ -59,8 +85,8 @@ int launch_gemm_q8q4_lds(const MfmaQ4Params& g, int mtiles, float* ws, size_t ws
     size_t lds = (size_t)nbz * 128 + (size_t)S * 2 * 4 * 1024;
     const size_t red = S > 1 ? (size_t)CW * S * CT * 16 * 64 * 4 : 0;
     if (red > lds) lds = red;
-    JHCHK(allow_lds((gemm_q8q4_lds_kernel<CW, CT, S, PK>), lds));
-    hipLaunchKernelGGL((gemm_q8q4_lds_kernel<CW, CT, S, PK>), dim3(8 * mtiles * gg, Z), dim3(CW * S * 64), lds, st, g, mtiles, nbz, Z > 1 ? ws : nullptr);
+    JHCHK(allow_lds((gemm_q8q4_lds_kernel<CW, CT, S>), lds));
+    hipLaunchKernelGGL((gemm_q8q4_lds_kernel<CW, CT, S>), dim3(8 * mtiles * gg, Z), dim3(CW * S * 64), lds, st, g, mtiles, nbz, Z > 1 ? ws : nullptr);
     HIPCHK(hipGetLastError());
     if (Z > 1) JHCHK(launch_splitk_reduce((const float*)ws, Z, g.m, g.n, g.n0, g.c, g.ldc, g.roffset, g.resid, st));
     return JH_OK;
@@ -87,7 +113,6 @@ int launch_gemm_q8q4_mfma(const MfmaQ4Params& g, hipStream_t st, bool tiled, flo
             while (SL > 1 && (size_t)nblk * 128 + (size_t)SL * 8192 > 150 * 1024) SL >>= 1;   // scale slice + the A rings of the SL K slices
             const bool lds_fits = (size_t)nblk * 128 + (size_t)SL * 8192 <= 150 * 1024;
             if (!lds_fits) CWL = -1;   // no instantiation below matches: the tile kernel takes it
-            if (CWL == 4 && CTL == 1 && SL == 2 && opt_int("JH_GEMM_LDS_PK", 0)) return launch_gemm_q8q4_lds<4, 1, 2, true>(g, mt, ws, ws_bytes, st);
 #define JH_LDS(CV, TV, SV) if (CWL == CV && CTL == TV && SL == SV) return launch_gemm_q8q4_lds<CV, TV, SV>(g, mt, ws, ws_bytes, st);
             JH_LDS(4, 1, 1) JH_LDS(4, 1, 2) JH_LDS(4, 1, 4) JH_LDS(2, 1, 2) JH_LDS(2, 1, 4) JH_LDS(2, 1, 8) JH_LDS(4, 2, 1) JH_LDS(4, 2, 2) JH_LDS(2, 2, 2)
             JH_LDS(1, 1, 4) JH_LDS(1, 1, 8) JH_LDS(2, 1, 1) JH_LDS(1, 1, 1) JH_LDS(1, 1, 2)
@@ -174,28 +199,6 @@ int launch_gemm_bf16_tile_mc(MfmaBf16TileParams g, int S, hipStream_t st) {
     if (S > 1) JHCHK(launch_splitk_reduce((const float*)g.ws, S, g.m, g.n, 0, g.c, g.ldc, 0, g.resid, st));
     return JH_OK;
 }
-// gemm_bf16_cw2_kernel: two column tiles per MFMA wave, A staged by a loader wave (jh_kernels.h).  128 columns per workgroup; K is
-// split (partials + reduce pass) only until the launch covers the chip.
-template <int MT>
-int launch_gemm_bf16_cw2(MfmaBf16TileParams g, int S, hipStream_t st) {
-    constexpr int PW = 4;                                    // 4 chunks x 4 slices x 2 KiB = 32 KiB of weights in flight per MFMA wave
-    g.nsplit = S;
-    const size_t lds = (size_t)2 * MT * 4 * 1024;
-    const int knock = opt_int("JH_BF16_CW2", 1);            // 11 / 12: knock-outs of the A / the weight stream (tools/gemm_bench.py; results wrong)
-    if (knock == 11 && MT == 5) {
-        JHCHK(allow_lds((gemm_bf16_cw2_kernel<5, PW, 1>), lds));
-        hipLaunchKernelGGL((gemm_bf16_cw2_kernel<5, PW, 1>), dim3(g.n / 128, S), dim3(BF16_CW2_WAVES * 64), lds, st, g);
-    } else if (knock == 12 && MT == 5) {
-        JHCHK(allow_lds((gemm_bf16_cw2_kernel<5, PW, 2>), lds));
-        hipLaunchKernelGGL((gemm_bf16_cw2_kernel<5, PW, 2>), dim3(g.n / 128, S), dim3(BF16_CW2_WAVES * 64), lds, st, g);
-    } else {
-        JHCHK(allow_lds((gemm_bf16_cw2_kernel<MT, PW>), lds));
-        hipLaunchKernelGGL((gemm_bf16_cw2_kernel<MT, PW>), dim3(g.n / 128, S), dim3(BF16_CW2_WAVES * 64), lds, st, g);
-    }
-    HIPCHK(hipGetLastError());
-    if (S > 1) JHCHK(launch_splitk_reduce((const float*)g.ws, S, g.m, g.n, 0, g.c, g.ldc, 0, g.resid, st));
-    return JH_OK;
-}
 // gemm_bf16_w8_kernel: 8 MFMA waves (4 column tiles x 2 K halves) + an LDS-DMA loader wave per workgroup; K additionally split over
 // grid.y (partials + reduce pass) until the launch covers the chip
 template <int MT>
@@ -211,42 +214,19 @@ int launch_gemm_bf16_w8(MfmaBf16TileParams g, int S, hipStream_t st) {
 // both operands in MFMA order (gemm_bf16_tile_kernel); n % 32 == 0, k % 16 == 0
 int launch_gemm_bf16_tile(const MfmaBf16TileParams& g, hipStream_t st) {
     const int mt = (g.m + 31) / 32, tiles = g.n / 32, nks = g.k / 16;
-    // prompt-sized M (2..6 row tiles) and whole 128-column groups: the 8-MFMA-wave kernel (round 6).  JH_BF16_W8=0 restores the
-    // round-5 dispatch below for comparisons.
-    if (opt_int("JH_BF16_W8", 1) && mt >= 2 && mt <= 6 && g.n % 128 == 0 && nks % 16 == 0) {
-        int S = 1;
+    // prompt-sized M (2..6 row tiles) and whole 128-column groups: the 8-MFMA-wave kernel (round 6)
+    if (mt >= 2 && mt <= 6 && g.n % 128 == 0 && nks % 16 == 0) {
+        int S = 1;   // fits(1) holds under this condition: every S chosen below fits
         auto fits = [&](int s2) { return nks % (16 * s2) == 0 && (s2 == 1 || (g.ws && (size_t)s2 * g.n <= (size_t)8 * 16384 && (g.n <= 8192 || s2 * g.m <= 512))); };
         while (S < 16 && fits(2 * S) && (g.n / 128) * 2 * S <= g_cu_count) S *= 2;   // one 9-wave workgroup per CU
         const int s_env3 = opt_int("JH_BF16_S", 0);
         if (s_env3 > 0 && fits(s_env3)) S = s_env3;
-        if (fits(S)) {
-            switch (mt) {
-                case 2: return launch_gemm_bf16_w8<2>(g, S, st);
-                case 3: return launch_gemm_bf16_w8<3>(g, S, st);
-                case 4: return launch_gemm_bf16_w8<4>(g, S, st);
-                case 5: return launch_gemm_bf16_w8<5>(g, S, st);
-                default: return launch_gemm_bf16_w8<6>(g, S, st);
-            }
-        }
-    }
-    // prompt-sized M (2..6 row tiles), whole 128-column groups and enough of them to cover the chip WITHOUT splitting K (gate|up of an
-    // 8B-class model: 224 groups): the loader-wave kernel, no reduce pass.  Everywhere else it measured equal or slower than the
-    // LDS kernel below with its K split (profiles/r05c_*): JH_BF16_CW2=2 forces it (with a K split) for comparisons.
-    const int cw2 = opt_int("JH_BF16_CW2", 1);
-    if (cw2 && mt >= 2 && mt <= 6 && g.n % 128 == 0 && nks % 16 == 0 && (cw2 >= 2 || (g.n / 128) * 4 >= g_cu_count * 3)) {
-        int S = 1;
-        const int s_env2 = opt_int("JH_BF16_S", 0);
-        if (g.ws && cw2 >= 2) {
-            auto fits = [&](int s2) { return nks % (16 * s2) == 0 && (size_t)s2 * g.n <= (size_t)8 * 16384 && (g.n <= 8192 || s2 * g.m <= 512); };
-            while (S < 16 && fits(2 * S) && (g.n / 128) * 2 * S <= g_cu_count) S *= 2;   // one workgroup per CU at most (3 waves of ~400 registers)
-            if (s_env2 > 0 && fits(s_env2)) S = s_env2;
-        }
         switch (mt) {
-            case 2: return launch_gemm_bf16_cw2<2>(g, S, st);
-            case 3: return launch_gemm_bf16_cw2<3>(g, S, st);
-            case 4: return launch_gemm_bf16_cw2<4>(g, S, st);
-            case 5: return launch_gemm_bf16_cw2<5>(g, S, st);
-            default: return launch_gemm_bf16_cw2<6>(g, S, st);
+            case 2: return launch_gemm_bf16_w8<2>(g, S, st);
+            case 3: return launch_gemm_bf16_w8<3>(g, S, st);
+            case 4: return launch_gemm_bf16_w8<4>(g, S, st);
+            case 5: return launch_gemm_bf16_w8<5>(g, S, st);
+            default: return launch_gemm_bf16_w8<6>(g, S, st);
         }
     }
     // waves per workgroup (column tiles sharing the A fragments through L1) vs workgroups: want >= ~2 workgroups per CU

@@ -35,25 +35,8 @@ namespace jh {
 constexpr int BF16R_GROUP = 128;   // elements of a row per 16-lane x 16-byte load
 static inline size_t bf16t_row_bytes(int K) { return (size_t)((K + BF16R_GROUP - 1) / BF16R_GROUP) * 256; }
 
-// BF16T copy of a row-major BF16 weight [nrows, ldw elements]: one thread per output 16-byte chunk; steps past K hold zeros
-// (never multiplied: the kernels stop at the row's last step).
-static __global__ __launch_bounds__(256) void bf16t_pack_kernel(const uint16_t* __restrict__ w, int nrows, int K, int ldw, uint8_t* __restrict__ out) {
-    const int G = (K + BF16R_GROUP - 1) / BF16R_GROUP;
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)nrows * G * 16) return;
-    const int t = (int)(idx & 15);
-    const long long rg = idx >> 4;
-    const int g = (int)(rg % G);
-    const long long row = rg / G;
-    const uint16_t* src = w + (size_t)row * ldw + (size_t)g * BF16R_GROUP;
-    i32x4 v = {0, 0, 0, 0};
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const int e = g * BF16R_GROUP + 32 * i;
-        if (e < K) v[i] = (int)((unsigned)src[32 * i + t] | ((unsigned)src[32 * i + 16 + t] << 16));
-    }
-    ((i32x4*)out)[((row >> 2) * G + g) * 64 + (row & 3) * 16 + t] = v;   // the rows of a quad interleaved per group, as in the P16T copies (jh_p16.h)
-}
+// BF16T copy (layout above) made by bf16t_pack_kernel (model.hip); steps past K hold zeros (never multiplied: the kernels stop at
+// the row's last step).
 
 // ------------------------------------------------------------------------------------------------ activation row in LDS
 struct ActBFR {

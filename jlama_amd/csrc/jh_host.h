@@ -254,8 +254,14 @@ int prefill_attn_half_bf16r(jh_session* s, int li, int rows, int start_pos, floa
 int prefill_ffn_half_bf16r(jh_session* s, int li, int rows, const float* x1, float* out, const float* resid, hipStream_t st);
 int prefill_chunk(jh_session* s, const int32_t* tokens, const float* x_in, bool x_in_dev, int rows, int start_pos, float* x_out, bool x_out_dev,
                   hipStream_t st);
+void launch_set_int(int* p, int v, hipStream_t st);
+void launch_embed_rows(const JWeight& emb, const int* tokens, int rows, int E, float* x, hipStream_t st);   // one row per token
+// pipeline.hip
+void launch_set_pos(DecodeState* d, int pos, hipStream_t st);
 // decode.hip
 int check_positions(const jh_session* s, int last_pos);
+void launch_set_state(DecodeState* d, int pos, int token, hipStream_t st);   // step 0, not done
+void launch_embed(const JWeight& emb, const DecodeState* d, int E, float* x, hipStream_t st);   // x = embedding row of d->token
 extern "C" {   // (defined between the C ABI entry points of decode.hip; hidden like everything that is not in include/jlama_hip.h)
 void drop_stale_graphs(jh_session* s);
 int attn_variant_for(const jh_session* s, int pos);

@@ -1113,26 +1113,6 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_bf16_mfma_kernel(MfmaGemmPara
             }
         }
 }
-// second pass of a split-K GEMM: C[i][j] = sum_s ws[s][i][j] (ascending K ranges => deterministic) (+ resid)
-static __global__ void splitk_reduce_kernel(const float* ws, int nsplit, int m, int n, int n0, float* c, int ldc, int roffset, const float* resid) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)m * n) return;
-    const int row = (int)(i / n), col = (int)(i % n);
-    float v = 0.0f;
-    for (int s = 0; s < nsplit; s++) v += ws[(size_t)s * m * n + i];
-    const size_t idx = (size_t)ldc * row + (n0 + col) - roffset;
-    c[idx] = resid ? v + resid[idx] : v;
-}
-// the same sums, four columns per thread (n, ldc, n0 - roffset multiples of 4; 16-byte aligned buffers): grid (n/4 / 256, m)
-static __global__ __launch_bounds__(256) void splitk_reduce4_kernel(const f32x4* ws, int nsplit, int m, int n4, f32x4* c, int ldc4, int coff4, const f32x4* resid) {
-    const int col = blockIdx.x * 256 + threadIdx.x, row = blockIdx.y;
-    if (col >= n4) return;
-    const size_t i = (size_t)row * n4 + col, stride = (size_t)m * n4;
-    f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-    for (int s = 0; s < nsplit; s++) v = v + ws[s * stride + i];
-    const size_t idx = (size_t)ldc4 * row + coff4 + col;
-    c[idx] = resid ? v + resid[idx] : v;
-}
 
 // ---- K3t: BF16 GEMM on MFMA-ordered operands (the prefill path of a BF16 model).
 // Both operands are tiled so that one wave-load is one MFMA operand, 1 KB contiguous:
@@ -1296,143 +1276,11 @@ __global__ __launch_bounds__(CWB * 64) void gemm_bf16_lds_kernel(MfmaBf16TilePar
             }
         }
 }
-// Round 5: the same GEMM with TWO column tiles per MFMA wave and a LOADER wave.
-// What bounded gemm_bf16_lds_kernel at M = 129 (tools/gemm_bf16_lab.hip, profiles/r04h_*): every MFMA read its A fragment from LDS
-// (1 KiB per 32-cycle instruction and SIMD = the LDS's 128 B/clk, so the matrix pipe idled at 58 cycles per MFMA even with no
-// global load at all), and the MFMA waves staged A themselves, so their waits for the young A loads (L2) were waits for every older
-// weight load (HBM) -- vector loads retire in order.  Here
-//   * an MFMA wave owns 2 adjacent column tiles: an A fragment read from LDS feeds 2 MFMAs (2 x MT accumulator tiles; 64 B/clk);
-//   * a third wave does nothing but stage A (global -> registers one chunk ahead -> LDS double buffer, one barrier per chunk), so the
-//     MFMA waves request WEIGHTS only, PW chunks of 4 k slices ahead (PW x 8 KiB per wave in flight);
-//   * 2 MFMA waves per workgroup = 128 columns: the un-split gate|up GEMM of an 8B-class model is 224 workgroups -- a workgroup per
-//     CU with NO split-K reduce pass; the smaller GEMMs split K until the chip is covered (partials + splitk_reduce4_kernel).
-// MFMA order inside an output element is the k-slice order, as before: results equal gemm_bf16_lds_kernel's bit for bit per split.
-constexpr int BF16_CW2_WAVES = 3;                            // 2 MFMA waves + the loader
-template <int MT, int PW, int KNOCK = 0>                     // KNOCK (measurement only, wrong results): 1 = the loader re-files chunk 0 (no A traffic), 2 = weights loaded once
-__global__ __launch_bounds__(BF16_CW2_WAVES * 64) void gemm_bf16_cw2_kernel(MfmaBf16TileParams p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int SLC = 4, PIECES = MT * SLC, NW = 2;
-    i32x4* ring = (i32x4*)smem;                              // [2][MT][SLC][64] x 16 B
-    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nks = p.k / 16, nsplit = p.nsplit > 1 ? p.nsplit : 1;
-    const int per = nks / nsplit, s0 = blockIdx.y * per;     // host: per % (PW * SLC) == 0
-    const int nchunks = per / SLC;
-    if (wv == NW) {
-        // ---- loader: A chunk c+2 requested while chunk c+1 is filed and chunk c is multiplied
-        const i32x4* ap = (const i32x4*)p.a + (size_t)s0 * 64 + lane;
-        const size_t a_rt = (size_t)nks * 64;
-        i32x4 r0[PIECES], r1[PIECES];
-        auto request = [&](i32x4 (&r)[PIECES], int c) __attribute__((always_inline)) {
-            c = c < nchunks ? c : nchunks - 1;
-            if (KNOCK == 1 && c > 1) return;
-#pragma unroll
-            for (int pc = 0; pc < PIECES; pc++) {
-                const int t = pc / SLC, q = pc - t * SLC;
-                r[pc] = ap[(size_t)t * a_rt + (size_t)(c * SLC + q) * 64];
-            }
-        };
-        auto file = [&](const i32x4 (&r)[PIECES], int buf) __attribute__((always_inline)) {
-#pragma unroll
-            for (int pc = 0; pc < PIECES; pc++) ring[((size_t)buf * PIECES + pc) * 64 + lane] = r[pc];
-        };
-        request(r0, 0);
-        request(r1, 1);
-        file(r0, 0);
-        lds_barrier();
-        for (int c = 0; c < nchunks; c += 2) {
-            request(r0, c + 2);
-            file(r1, 1);
-            lds_barrier();
-            request(r1, c + 3);
-            file(r0, 0);
-            lds_barrier();
-        }
-        return;
-    }
-    const int nl = lane & 31, h = lane >> 5;
-    const int ct0 = (blockIdx.x * NW + wv) * 2;              // host: n % 128 == 0
-    const i32x4* wp0 = (const i32x4*)p.w + ((size_t)ct0 * nks + s0) * 64 + lane;
-    const i32x4* wp1 = wp0 + (size_t)nks * 64;
-    f32x16 acc0[MT], acc1[MT];
-#pragma unroll
-    for (int t = 0; t < MT; t++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) { acc0[t][r] = 0.0f; acc1[t][r] = 0.0f; }
-    const int last = per - 1;
-    i32x4 wr0[PW][SLC], wr1[PW][SLC];
-    auto load_w = [&](i32x4 (&w0)[SLC], i32x4 (&w1)[SLC], int sl0) __attribute__((always_inline)) {
-#pragma unroll
-        for (int q = 0; q < SLC; q++) {
-            int sl = sl0 + q;
-            sl = sl < last ? sl : last;
-            if (KNOCK == 2 && sl0 >= PW * SLC) continue;
-            w0[q] = __builtin_nontemporal_load(wp0 + (size_t)sl * 64);
-            w1[q] = __builtin_nontemporal_load(wp1 + (size_t)sl * 64);
-        }
-    };
-    auto read_a = [&](i32x4 (&av)[MT], int buf, int q) __attribute__((always_inline)) {
-#pragma unroll
-        for (int t = 0; t < MT; t++) av[t] = ring[((size_t)buf * PIECES + t * SLC + q) * 64 + lane];
-    };
-    auto mma_slice = [&](const i32x4 (&av)[MT], const i32x4& w0, const i32x4& w1) __attribute__((always_inline)) {
-        const bf16x8 b0 = __builtin_bit_cast(bf16x8, w0), b1 = __builtin_bit_cast(bf16x8, w1);
-#pragma unroll
-        for (int t = 0; t < MT; t++) {
-            const bf16x8 a = __builtin_bit_cast(bf16x8, av[t]);
-            acc0[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b0, acc0[t], 0, 0, 0);
-            acc1[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b1, acc1[t], 0, 0, 0);
-        }
-    };
-    auto mma_chunk = [&](int buf, const i32x4 (&w0)[SLC], const i32x4 (&w1)[SLC]) __attribute__((always_inline)) {
-        i32x4 a0[MT], a1[MT];                                // A fragments are read a slice ahead of their MFMAs
-        read_a(a0, buf, 0);
-#pragma unroll
-        for (int q = 0; q < SLC; q += 2) {
-            read_a(a1, buf, q + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            mma_slice(a0, w0[q], w1[q]);
-            __builtin_amdgcn_sched_barrier(0);
-            if (q + 2 < SLC) read_a(a0, buf, q + 2);
-            __builtin_amdgcn_sched_barrier(0);
-            mma_slice(a1, w0[q + 1], w1[q + 1]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-#pragma unroll
-    for (int i = 0; i < PW; i++) load_w(wr0[i], wr1[i], i * SLC);
-    lds_barrier();
-    for (int c = 0; c < nchunks; c += PW) {
-#pragma unroll
-        for (int i = 0; i < PW; i++) {
-            mma_chunk(i & 1, wr0[i], wr1[i]);                // PW is even: chunk c + i sits in buffer i & 1
-            load_w(wr0[i], wr1[i], (c + i + PW) * SLC);
-            lds_barrier();
-        }
-    }
-#pragma unroll
-    for (int cc = 0; cc < 2; cc++) {
-        const int ncol = (ct0 + cc) * 32 + nl;
-#pragma unroll
-        for (int t = 0; t < MT; t++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int mrow = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                const float v = cc ? acc1[t][r] : acc0[t][r];
-                if (mrow < p.m) {
-                    if (nsplit > 1) {
-                        p.ws[((size_t)blockIdx.y * p.m + mrow) * p.n + ncol] = v;
-                    } else {
-                        const size_t idx = (size_t)p.ldc * mrow + ncol;
-                        p.c[idx] = p.resid ? v + p.resid[idx] : v;
-                    }
-                }
-            }
-    }
-}
-// Round 6: the same GEMM with EIGHT MFMA waves per workgroup.  What bounded gemm_bf16_cw2_kernel at M = 129
-// was not the memory system (tools/chain_lab.hip: a CU fills 85-105 GB/s from an L2-resident buffer with 4-8 waves, not the ~30 GB/s
-// DESIGN assumed for the activation re-reads): its two MFMA waves sat on two of the CU's four SIMDs and issued a 32x32x16 every
-// 56-64 cycles each -- an issue-rate ceiling of ~4 TB/s of weights, reached at half that.  Here
+// Round 6: the same GEMM with EIGHT MFMA waves per workgroup.  What bounded round 5's loader-wave form (two MFMA
+// waves + one A loader per workgroup; since removed) at M = 129 was not the memory system (tools/chain_lab.hip: a CU fills 85-105 GB/s
+// from an L2-resident buffer with 4-8 waves, not the ~30 GB/s DESIGN assumed for the activation re-reads): its two MFMA waves sat on
+// two of the CU's four SIMDs and issued a 32x32x16 every 56-64 cycles each -- an issue-rate ceiling of ~4 TB/s of weights, reached
+// at half that.  Here
 //   * 8 MFMA waves = 4 column tiles (128 columns) x 2 halves of the workgroup's K range: two waves per SIMD, every matrix pipe
 //     busy, 8 x PW x 4 KiB of weights in flight per CU; each wave keeps MT accumulator tiles (all prompt rows) of ITS half;
 //   * a ninth wave stages the A chunks of BOTH halves with LDS-DMA (global_load_lds_dwordx4: no registers, no ds_write; 1 KiB per
@@ -1865,7 +1713,7 @@ __global__ __launch_bounds__(S * CW * 64) __attribute__((amdgpu_waves_per_eu(3))
 // resident waves per SIMD: S waves of a workgroup split the K range of each column tile (own A ring per slice, partial tiles
 // meet in LDS, ascending order) -- at M = 129 one wave per output tile is 2.2 waves per SIMD for the whole launch.
 // grid.y = further K slices across workgroups (small N): partials go to a workspace [slice][m][n], splitk_reduce_kernel adds them.
-template <int CW, int CT, int S, bool PK = false>
+template <int CW, int CT, int S>
 __global__ __launch_bounds__(CW * S * 64) void gemm_q8q4_lds_kernel(MfmaQ4Params p, int mtiles, int nbz, float* part) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1945,18 +1793,8 @@ __global__ __launch_bounds__(CW * S * 64) void gemm_q8q4_lds_kernel(MfmaQ4Params
                 const i32x16 z16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
                 const i32x16 d = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bw, z16, 0, 0, 0);
                 const float s16 = sv[q][t] * 0.0625f;
-                if constexpr (PK) {   // experiment: the packed forms
 #pragma unroll
-                    for (int r = 0; r < 16; r += 2) {
-                        const f32x2 pp = f32x2{da[r], da[r + 1]} * s16;
-                        const f32x2 dd = f32x2{(float)d[r], (float)d[r + 1]};
-                        const f32x2 aa = __builtin_elementwise_fma(pp, dd, f32x2{acc[t][r], acc[t][r + 1]});
-                        acc[t][r] = aa.x; acc[t][r + 1] = aa.y;
-                    }
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 16; r++) acc[t][r] = fma1(mul1(da[r], s16), (float)d[r], acc[t][r]);   // the conversion stays visible to hipcc: it owns the MFMA -> VALU hazard
-                }
+                for (int r = 0; r < 16; r++) acc[t][r] = fma1(mul1(da[r], s16), (float)d[r], acc[t][r]);   // the conversion stays visible to hipcc: it owns the MFMA -> VALU hazard
                 // pin this tile's scaling here (the optimizer otherwise sinks all the VALU work below the chunk's last MFMA and
                 // keeps eight result tiles live): the accumulators pass through an opaque asm
                 asm volatile("" : "+v"(acc[t][0]), "+v"(acc[t][1]), "+v"(acc[t][2]), "+v"(acc[t][3]), "+v"(acc[t][4]), "+v"(acc[t][5]),
@@ -2019,28 +1857,6 @@ __global__ __launch_bounds__(CW * S * 64) void gemm_q8q4_lds_kernel(MfmaQ4Params
     }
 }
 
-static __global__ void add_rows_kernel(const float* a, const float* b, float* out, int n) {   // out = a + b (residual add)
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = a[i] + b[i];
-}
-static __global__ void set_int_kernel(int* p, int v) { *p = v; }
-// tensor-parallel one-shot reduction: a shard's partial [E] goes straight into its slot of EVERY shard's
-// slot buffer (peer stores over xGMI when the destination lives on another device) ...
-static __global__ void tp_scatter_kernel(const float* part, float* const* dst, int n_dst, int E) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= E) return;
-    const float v = part[i];
-    for (int j = 0; j < n_dst; j++) dst[j][i] = v;
-}
-// ... and every shard sums the N slots locally, in shard order 0..N-1 (the lock-step order: results never depend on which
-// peer arrived first)
-static __global__ void tp_sum_kernel(const float* slots, int n, int E, float* out, size_t stride) {   // stride: floats between two shards' slots
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= E) return;
-    float v = slots[i];
-    for (int k = 1; k < n; k++) v = v + slots[k * stride + i];
-    out[i] = v;
-}
 // ---- the same reduction without the host in it: every shard replays ONE captured graph per token, the shards meet in kernels.
 // A shard's scatter workgroup b stores its 256 elements into its slot on every shard (system-scope stores: peer memory over
 // xGMI), fences, then raises its flag word b on every shard to the sequence number of this (token, layer); the consumer's
@@ -2069,83 +1885,6 @@ __device__ __forceinline__ bool tp_wait_ge(const unsigned* f, unsigned want, uns
     }
     return true;
 }
-static __global__ __launch_bounds__(256) void tp_scatter_flag_kernel(const float* part, float* const* dst, unsigned* const* fdst, int n_dst, int E,
-                                                              const unsigned* seqp, int li, int L) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < E) {
-        const float v = part[i];
-        for (int j = 0; j < n_dst; j++) st_sys(dst[j] + i, v);
-    }
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned seq = *seqp * (unsigned)L + (unsigned)li + 1u;
-        for (int j = 0; j < n_dst; j++) __hip_atomic_store(fdst[j] + blockIdx.x, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
-static __global__ __launch_bounds__(256) void tp_sum_wait_kernel(const float* slots, const unsigned* flags, int n, int E, int nwg, unsigned* seqp,
-                                                          int li, int L, const float* resid, float* out) {
-    const unsigned seq = *seqp * (unsigned)L + (unsigned)li + 1u;
-    if ((int)threadIdx.x < n) tp_wait_ge(flags + (size_t)threadIdx.x * nwg + blockIdx.x, seq, seqp + 1);
-    __syncthreads();
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= E) return;
-    float v = ld_sys(slots + i);
-    for (int k = 1; k < n; k++) v = v + ld_sys(slots + (size_t)k * E + i);   // shard order: the lock-step order
-    out[i] = resid[i] + v;                                                      // TransformerBlock.java:185 / :203
-}
-// the same meeting when the producers were the o-proj / down GEMVs themselves (GemvParams::tp_*): their workgroups own row ranges
-// that depend on the launch plan, so every consumer workgroup waits for ALL nflags workgroup flags of the N producers (a few
-// hundred words polled by 16 workgroups -- not the 256 x 256 of a grid barrier)
-static __global__ __launch_bounds__(256) void tp_sum_wait_all_kernel(const float* slots, const unsigned* flags, int n, int E, int nflags, int stride,
-                                                              unsigned* seqp, int li, int L, const float* resid, float* out) {
-    const unsigned seq = *seqp * (unsigned)L + (unsigned)li + 1u;
-    {   // a thread's flags are polled TOGETHER (independent loads, one memory round trip per sweep), bounded like tp_wait_ge
-        const long long t0 = wall_clock64();
-        unsigned* err = seqp + 1;
-        for (;;) {
-            bool all = true;
-            for (int i = threadIdx.x; i < n * nflags; i += 256)
-                all &= __hip_atomic_load(flags + (size_t)(i / nflags) * stride + (i % nflags), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) >= seq;
-            if (all) break;
-            if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
-            if (wall_clock64() - t0 > tp_wait_bound(err)) { __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-            __builtin_amdgcn_s_sleep(2);
-        }
-    }
-    __syncthreads();
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= E) return;
-    float v = ld_sys(slots + i);
-    for (int k = 1; k < n; k++) v = v + ld_sys(slots + (size_t)k * E + i);   // shard order: the lock-step order
-    out[i] = resid[i] + v;                                                      // TransformerBlock.java:185 / :203
-}
-// shard 0, after finish_token_kernel: the next row (token, position) to every other shard's mailbox
-static __global__ void tp_publish_token_kernel(const DecodeState* st, TPMail* const* mails, int n, const unsigned* seqp) {
-    if (threadIdx.x >= (unsigned)n) return;
-    TPMail* m = mails[threadIdx.x];
-    __hip_atomic_store(&m->token, st->token, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(&m->pos, st->pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __threadfence_system();
-    __hip_atomic_store(&m->seq, *seqp + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-// the other shards, first node of their token graph: wait for the row of this replay, take it over
-static __global__ void tp_wait_token_kernel(const TPMail* mail, unsigned* seqp, DecodeState* st) {
-    tp_wait_ge(&mail->seq, *seqp, seqp + 1);
-    st->token = __hip_atomic_load(&mail->token, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    st->pos = __hip_atomic_load(&mail->pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-static __global__ void tp_bump_seq_kernel(unsigned* seqp) { *seqp = *seqp + 1u; }
-static __global__ void set_pos_kernel(DecodeState* st, int pos) { st->pos = pos; }   // pipeline stages: the token / step words stay
-// one pipeline stage per process: the token id arrives in device memory (shipped by the last stage), never through the host
-static __global__ void set_state_dev_kernel(DecodeState* st, int pos, const int* token_dev) {
-    st->pos = pos; st->step = 0; st->done = 0;
-    if (token_dev) st->token = *token_dev;
-}
-static __global__ void store_token_kernel(const DecodeState* st, int* out) { *out = st->token; }
-static __global__ void set_state_kernel(DecodeState* st, int pos, int token, int step) {
-    st->pos = pos; st->token = token; st->step = step; st->done = 0;
-}
 
 // EmbedInput for a Q4 / BF16 / F32 table (core/model/llama/LlamaModel.java:67-98): x[j] = (nib-8)*scale
 __device__ __forceinline__ void embed_row(const void* table, const float* scales, int dtype, int token, int E,
@@ -2169,31 +1908,11 @@ __device__ __forceinline__ void embed_row(const void* table, const float* scales
     }
 }
 
-static __global__ void embed_kernel(const void* table, const float* scales, int dtype, const DecodeState* st, int E,
-                             float* x) {
-    embed_row(table, scales, dtype, st->token, E, x);
-}
-
-// argmax over the LM head's per-workgroup partials -> next token; advance the decode state and look up the
-// next embedding row, so a greedy decode step needs no host round trip (AbstractModel.java:590-599).
-// Stop tokens (Config.eosTokens, AbstractModel.java:600-603): the step that samples one is the last; st->done freezes
-// the state, so the remaining replays of an already-queued decode loop emit nothing.
 // ---- temperature sampling inside the device loop (AbstractModel.sample, core/model/AbstractModel.java:471-489):
 //   v_i = (float)exp((logit_i - max) / T) in double;  sum = float running sum over i in INDEX ORDER;  acc += v_i / sum until
-//   acc >= u -> token i (V-1 if never).  The exponentials are independent (sample_exp_kernel, whole chip); the two float
+//   acc >= u -> token i (V-1 if never).  The exponentials are independent (sample_exp_kernel, layers.hip, whole chip); the two float
 //   accumulations are defined by their index order -- sample_pick_kernel below reproduces them bit for bit -- and a T > 0
 //   generation stays at one graph replay per token, no host round trip.
-static __global__ __launch_bounds__(256) void sample_exp_kernel(const float* logits, int V, const float* partv, int nparts, float temperature, float* prob) {
-    __shared__ float red[4];
-    float m = -INFINITY;
-    for (int i = threadIdx.x; i < nparts; i += 256) m = fmaxf(m, partv[i]);   // the LM head's per-workgroup maxima
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    const double maxv = (double)fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < V) prob[i] = (float)exp(((double)logits[i] - maxv) / (double)temperature);
-}
 // The two accumulations, exactly, by 1024 lanes (jh_seqsum.h).  The values are taken in windows of 1024 x SAMPLE_E: a lane owns
 // SAMPLE_E consecutive values (coalesced 16-byte loads, transposed through LDS), adds them to the two reference values of the
 // running sum's binade (2 float adds per value), a scan composes the lanes' parity -> increment maps, and the first lane whose
@@ -2358,11 +2077,6 @@ __global__ __launch_bounds__(SAMPLE_T) void sample_sum_kernel(const float* prob,
     seq_pass<SAMPLE_T, SAMPLE_E>(prob, V, INFINITY, sh, (float*)smem, sum, pick);   // AbstractModel.java:475-480
     if (threadIdx.x == 0) *sum_out = sum;
 }
-static __global__ __launch_bounds__(256) void sample_norm_kernel(float* prob, int V, const DecodeState* st, const float* sum) {
-    if (st->done) return;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < V) prob[i] = prob[i] / *sum;                              // :481-483
-}
 template <int SAMPLE_T, int SAMPLE_E>
 __global__ __launch_bounds__(SAMPLE_T) void sample_pick_kernel(const float* prob, int V, const float* u, const DecodeState* st, int* tok_out) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -2372,48 +2086,6 @@ __global__ __launch_bounds__(SAMPLE_T) void sample_pick_kernel(const float* prob
     int pick;
     seq_pass<SAMPLE_T, SAMPLE_E>(prob, V, u[st->step], sh, (float*)smem, acc, pick);   // :484-489
     if (threadIdx.x == 0) *tok_out = pick >= 0 ? pick : V - 1;
-}
-
-static __global__ void finish_token_kernel(const float* partv, const int* parti, int nparts, DecodeState* st,
-                                    int* out_tokens, const void* table, const float* scales, int dtype, int E,
-                                    float* x, int do_embed, const int* eos,   // eos: [count, id0, id1, ...] (jh_session_set_eos)
-                                    const int* forced) {                      // non-null: the sampled id (sample_pick_kernel) replaces the argmax
-    __shared__ float sv[16];
-    __shared__ int si[16];
-    __shared__ int tok;
-    if (st->done) return;   // uniform: every thread reads the same word
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
-        const float v = partv[i];
-        const int id = parti[i];
-        if (v > bv || (v == bv && id < bi)) { bv = v; bi = id; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o);
-        const int oi = __shfl_xor(bi, o);
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    if (lane == 0) { sv[wave] = bv; si[wave] = bi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 0; w < nw; w++)
-            if (sv[w] > bv || (sv[w] == bv && si[w] < bi)) { bv = sv[w]; bi = si[w]; }
-        if (forced) bi = *forced;
-        tok = bi;
-        out_tokens[st->step] = bi;
-        st->token = bi;
-        st->pos = st->pos + 1;
-        st->step = st->step + 1;
-        int stop = 0;
-        const int n_eos = eos[0];
-        for (int i = 0; i < n_eos; i++) stop |= (eos[1 + i] == bi);
-        st->done = stop;
-    }
-    __syncthreads();
-    if (do_embed) embed_row(table, scales, dtype, tok, E, x);
 }
 
 // ------------------------------------------------------------------------------------------------ K4: decode attention
@@ -2928,48 +2600,6 @@ __global__ __launch_bounds__(256) void rows_bf16_kernel(RowsParams p) {
     }
 }
 
-// Re-tile a row-major weight into MFMA order for the prefill GEMMs:
-//   Q4   [N][K/2] (+ scales [N][K/32])  ->  wt [N/32][K/32][32 rows][16 B],  st [N/32][K/32][32]
-//   BF16 [N][K]                         ->  wt [N/32][K/16][h][32 rows][8 values]
-// At streaming rate, for both weight types (it also runs in front of every prefill GEMM when the MFMA-ordered copy is NOT kept
-// resident, JH_TILED_COPY=transient):  a weight row is `nch` 16-byte chunks (Q4: one block of 32 nibbles; BF16: 8 values --
-// the [k slice][h] pair is chunk index c8 = 2*ksl + h, so both layouts are dst = ((panel*nch + chunk)*32 + row)*16 B), the
-// destination is [N/32][nch][32 rows][16 B] (+ Q4 scales [N/32][nch][32]).  One workgroup moves a 32-row x 64-chunk tile
-// through LDS: reads are 1 KiB contiguous per wave (a row's 64 chunks), writes 1 KiB contiguous per wave (2 chunks x 32 rows).
-// LDS rows are padded by one chunk so that the transposed ds_read_b128 (32 lanes = 32 rows of one chunk) is conflict-free.
-static __global__ __launch_bounds__(256) void retile16_kernel(const i32x4* __restrict__ w, const float* __restrict__ ws, int N, int nch,
-                                                       i32x4* __restrict__ wt, float* __restrict__ st) {
-    __shared__ i32x4 tile[32 * 65];
-    __shared__ float stile[32 * 65];
-    const int panel = blockIdx.y, c0 = blockIdx.x * 64;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int cin = c0 + lane;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const int r = wave + 4 * i;
-        if (cin < nch) {
-            const size_t src = (size_t)(panel * 32 + r) * nch + cin;
-            tile[r * 65 + lane] = __builtin_nontemporal_load(w + src);
-            if (ws) stile[r * 65 + lane] = __builtin_nontemporal_load(ws + src);
-        }
-    }
-    __syncthreads();
-    const int row = lane & 31, hh = lane >> 5;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const int cl = 2 * (wave + 4 * i) + hh;        // chunk within the tile
-        if (c0 + cl < nch) {
-            const size_t dst = ((size_t)panel * nch + c0 + cl) * 32 + row;
-            wt[dst] = tile[row * 65 + cl];
-            if (ws) st[dst] = stile[row * 65 + cl];
-        }
-    }
-}
-
-static __global__ void embed_rows_kernel(const void* table, const float* scales, int dtype, const int* tokens, int E, float* x) {
-    embed_row(table, scales, dtype, tokens[blockIdx.x], E, x + (size_t)blockIdx.x * E);
-}
-
 struct PrefillAttnParams {
     float* qkv; int ldqkv;        // [rows][A + 2*KV] F32: q | k | v per row (q is rotated in place)
     const float* rope;
@@ -2981,31 +2611,6 @@ struct PrefillAttnParams {
     float scale;
     float* out; int ldo;          // [rows][A]
 };
-
-// RoPE of q (in place) and k, and the KV page writes, for every row of the chunk (CausalSelfAttention.java:199-286;
-// the table offset is position*half + kvHead*headSize for q and k alike -- SURVEY.md 8a "RoPE quirk").
-static __global__ __launch_bounds__(256) void rows_rope_kv_kernel(PrefillAttnParams p) {
-    const int row = blockIdx.x, pos = p.start_pos[0] + row;
-    const int HS = p.head_size, half = HS / 2, A = p.n_heads * HS, KV = p.n_kv_heads * HS, group = p.n_heads / p.n_kv_heads;
-    float* r = p.qkv + (size_t)row * p.ldqkv;
-    float* krow = (float*)kv_row(p, 0, pos, KV);
-    float* vrow = (float*)kv_row(p, 1, pos, KV);
-    const int npairs = (p.n_heads + p.n_kv_heads) * half;
-    const int t0 = blockIdx.y * blockDim.x + threadIdx.x, tstep = blockDim.x * gridDim.y;   // gridDim.y workgroups per row
-    for (int i = t0; i < npairs; i += tstep) {
-        const int hh = i / half, d = i - hh * half;
-        const bool isq = hh < p.n_heads;
-        const int kvh = isq ? hh / group : hh - p.n_heads;
-        const float* rf = p.rope + ((size_t)pos * half + (size_t)(kvh + p.kv_head_offset) * HS) * 2;
-        float* v = isq ? r + (size_t)hh * HS : r + A + (size_t)kvh * HS;
-        const float a = v[d], b = v[d + half], c = rf[2 * d], s = rf[2 * d + 1];
-        const float r0 = a * c - b * s;
-        const float r1 = a * s + b * c;
-        if (isq) { v[d] = r0; v[d + half] = r1; }
-        else { krow[(size_t)kvh * HS + d] = r0; krow[(size_t)kvh * HS + d + half] = r1; }
-    }
-    for (int i = t0; i < KV; i += tstep) vrow[i] = r[A + KV + i];
-}
 
 // Causal attention of one chunk row against positions [0, start_pos+row]: workgroup = (kv head, row), the GROUP query
 // heads of the kv head share every K/V load.  Scores -> softmax ((float)exp in double, division) -> weighted V sum, as
@@ -3262,28 +2867,6 @@ __global__ __launch_bounds__(GROUP * 64) void attn_prefill_mfma_kernel(PrefillAt
 }
 static inline size_t prefill_mfma_lds(int hs, int group) { return ((size_t)32 * (hs + 4) + 32 * hs + (size_t)group * 32 * 33 + group * 32) * 4; }
 
-// merge the key-range splits of attn_prefill_mfma_kernel: w_s = exp(m_s - M), out = sum_s w_s O_s / sum_s w_s l_s (split order)
-static __global__ __launch_bounds__(128) void attn_prefill_combine_kernel(PrefillAttnParams p, PrefillMfmaExtra e) {
-    const int row = blockIdx.x, head = blockIdx.y, HS = p.head_size;
-    const float* ml = e.ws_ml + ((size_t)row * p.n_heads + head) * e.nsplit * 2;
-    float M = -INFINITY;
-    for (int s = 0; s < e.nsplit; s++) M = fmaxf(M, ml[2 * s]);
-    float L = 0.0f;
-    for (int s = 0; s < e.nsplit; s++) {
-        const float w = ml[2 * s] == -INFINITY ? 0.0f : (float)exp((double)(ml[2 * s] - M));
-        L += ml[2 * s + 1] * w;
-    }
-    const float* ob = e.ws_o + ((size_t)row * p.n_heads + head) * e.nsplit * HS;
-    for (int d = threadIdx.x; d < HS; d += blockDim.x) {
-        float o = 0.0f;
-        for (int s = 0; s < e.nsplit; s++) {
-            const float w = ml[2 * s] == -INFINITY ? 0.0f : (float)exp((double)(ml[2 * s] - M));
-            o = fmaf(ob[(size_t)s * HS + d], w, o);
-        }
-        p.out[(size_t)row * p.ldo + (size_t)head * HS + d] = o / L;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ Tier-1 generic kernels
 // One wave per output element C[i, j]; lanes stride over K.  Correct for every offset/stride combination the
 // reference's C entry points accept (nc/simd/vector_simd.h:22-38); used for M>1, windows, F32/BF16 operands.
@@ -3355,146 +2938,6 @@ __global__ void ew_kernel(float* a, const float* b, float f, int n) {
     else if (OP == EW_SCALE) a[i] = a[i] * f;
     else if (OP == EW_SAXPY) a[i] = fmaf(b[i], f, a[i]);
     else a[i] = silu_ref(a[i]) * b[i];
-}
-static __global__ void acc_q4_kernel(float* a, const uint8_t* nib, const float* sc, int offset, int n) {
-    const int i = offset + blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= offset + n) return;
-    const int blk = i / 32, in = i % 32;
-    const uint8_t b = nib[blk * 16 + (in & 15)];
-    const int x = (in < 16) ? (b & 0x0F) - 8 : ((b >> 4) & 0x0F) - 8;
-    a[i] = a[i] + (float)x * sc[blk];
-}
-// batched saxpy: thread per element, fma chain over rows in ascending order (PTO:2648-2698)
-static __global__ void saxpy_batch_kernel(const float* alpha, const float* x, int ldx, float* y, int limit, int rows) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= limit) return;
-    float acc = y[t];
-    for (int n = 0; n < rows; n++) acc = fmaf(x[(size_t)n * ldx + t], alpha[n], acc);
-    y[t] = acc;
-}
-// quantize F32 -> I8 (PTO:1684-1723): one 32-lane half-wave per block
-static __global__ void quantize_q8_kernel(const float* x, int rows, int ldx, int offset, int length, int8_t* q, int ldq,
-                                   float* d, int ldd) {
-    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    const int hw = gid >> 5, l = gid & 31;
-    const int bpr = length / QB;
-    if (hw >= rows * bpr) return;
-    const int r = hw / bpr, blk = hw % bpr;
-    const int e = offset + blk * QB + l;
-    const float y = x[(size_t)r * ldx + e];
-    float amax = fabsf(y);
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
-    const float dd = amax / 127.0f;
-    const float id = (amax != 0.0f) ? 127.0f / amax : 0.0f;
-    float v = y * id;
-    v = v + 0.5f;
-    q[(size_t)r * ldq + e] = (int8_t)f2b(v);
-    if (l == 0) d[(size_t)r * ldd + e / QB] = dd;
-}
-static __global__ void widen_bf16_kernel(const uint16_t* in, long long n, float* out) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = bf16_to_f32(in[i]);
-}
-static __global__ void quantize_bf16_kernel(const float* x, long long n, uint16_t* out) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = f32_to_bf16(x[i]);
-}
-// BF16 result tensor of a Tier-1 GEMM: out[i*ld + j] = bf16(in[i*ld + j]) for j < n, one grid row per matrix row
-static __global__ void store_bf16_2d_kernel(const float* in, uint16_t* out, int n, int ld) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n) out[(size_t)blockIdx.y * ld + j] = f32_to_bf16(in[(size_t)blockIdx.y * ld + j]);
-}
-// RMSNorm.forward (core/model/RMSNorm.java:33-56), single workgroup per row
-static __global__ __launch_bounds__(1024) void rmsnorm_kernel(const float* x, const float* w, float adj, int n, float eps,
-                                                       float* out) {
-    __shared__ double red[32];
-    double ss = 0.0;
-    for (int j = threadIdx.x; j < n; j += blockDim.x) { const float v = x[j]; ss += (double)(v * v); }
-    ss = block_sum_d(ss, red);
-    ss /= (double)n;
-    ss += (double)eps;
-    ss = 1.0 / sqrt(ss);
-    const float fs = (float)ss;
-    for (int j = threadIdx.x; j < n; j += blockDim.x) out[j] = (adj + w[j]) * (fs * x[j]);
-}
-// VectorMath.softMax (core/math/VectorMath.java:69-90), single workgroup
-// LayerNorm.forward (core/model/LayerNorm.java:41-67), GPT-2's norm: FLOAT sums accumulated in index order (one lane
-// walks the row so the running sums round exactly as the Java loop's), var = sumSq/E - mean^2,
-// 1/(float)sqrt(var+eps), then ((x-mean)*inv)*w + b with no fused multiply-add.  One wave per row.
-static __global__ __launch_bounds__(64) void layernorm_kernel(const float* x, const float* w, const float* b, int ld, int offset, int length,
-                                                       int divisor, float eps, float* out) {
-    const float* row = x + (size_t)blockIdx.x * ld;
-    float* orow = out + (size_t)blockIdx.x * ld;
-    __shared__ float stats[2];
-    if (threadIdx.x == 0) {
-        float sum = 0.0f, sumsq = 0.0f;
-        for (int i = offset; i < offset + length; i++) {
-            const float v = row[i];
-            sum += v;
-            sumsq += v * v;
-        }
-        const float mean = sum / (float)divisor;
-        const float variance = sumsq / (float)divisor - mean * mean;
-        stats[0] = mean;
-        stats[1] = 1.0f / (float)sqrt((double)(variance + eps));
-    }
-    __syncthreads();
-    const float mean = stats[0], inv = stats[1];
-    for (int i = offset + threadIdx.x; i < offset + length; i += blockDim.x) orow[i] = (row[i] - mean) * inv * w[i] + b[i];
-}
-// ActivationFunction.eval GELU (core/math/ActivationFunction.java:32-34): tanh approximation evaluated in double
-static __global__ void gelu_kernel(float* x, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double v = (double)x[i];
-    x[i] = (float)(0.5 * v * (1.0 + tanh(sqrt(2.0 / 3.14159265358979323846) * (v + 0.044715 * pow(v, 3.0)))));
-}
-static __global__ __launch_bounds__(1024) void softmax_kernel(float* x, int offset, int length) {
-    __shared__ float redf[32];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    float m = -INFINITY;
-    for (int i = offset + threadIdx.x; i < offset + length; i += blockDim.x) m = fmaxf(m, x[i]);
-    m = wave_max(m);
-    if (lane == 0) redf[wave] = m;
-    __syncthreads();
-    m = redf[0];
-    for (int i = 1; i < nw; i++) m = fmaxf(m, redf[i]);
-    __syncthreads();
-    float s = 0.0f;
-    for (int i = offset + threadIdx.x; i < offset + length; i += blockDim.x) {
-        const float e = (float)exp((double)(x[i] - m));
-        x[i] = e;
-        s += e;
-    }
-    s = wave_sum(s);
-    if (lane == 0) redf[wave] = s;
-    __syncthreads();
-    s = 0.0f;
-    for (int i = 0; i < nw; i++) s += redf[i];
-    for (int i = threadIdx.x; i < offset + length; i += blockDim.x) x[i] = x[i] / s;  // reference divides from index 0
-}
-// RoPE rotation, GQA branch (core/model/CausalSelfAttention.java:247-286)
-static __global__ void rope_kernel(float* q, float* k, const float* rope, int position, int n_heads, int n_kv_heads, int hs) {
-    const int half = hs / 2, group = n_heads / n_kv_heads;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int poffset = position * half;
-    if (i < n_heads * half) {
-        const int h = i / half, d = i % half;
-        const int g = (h / group) * hs + d;
-        const float fcr = rope[(size_t)(poffset + g) * 2], fci = rope[(size_t)(poffset + g) * 2 + 1];
-        const float q0 = q[h * hs + d], q1 = q[h * hs + d + half];
-        q[h * hs + d] = q0 * fcr - q1 * fci;
-        q[h * hs + d + half] = q0 * fci + q1 * fcr;
-    } else if (i < (n_heads + n_kv_heads) * half) {
-        const int ii = i - n_heads * half;
-        const int h = ii / half, d = ii % half;
-        const int g = h * hs + d;
-        const float fcr = rope[(size_t)(poffset + g) * 2], fci = rope[(size_t)(poffset + g) * 2 + 1];
-        const float k0 = k[h * hs + d], k1 = k[h * hs + d + half];
-        k[h * hs + d] = k0 * fcr - k1 * fci;
-        k[h * hs + d + half] = k0 * fci + k1 * fcr;
-    }
 }
 
 }  // namespace jh

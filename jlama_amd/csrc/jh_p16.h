@@ -50,37 +50,8 @@ __device__ __forceinline__ int perm_b(int hi_src, int lo_src, int sel) {   // se
 }
 
 // P16T copy of a Q4 weight: row stride G * 256 bytes (G = groups of 16 blocks, the last one zero-padded); inside a group the 16-byte
-// chunk t holds nibble pair t (elements t and t+16) of the group's 16 blocks, four blocks per dword in the nibble order below.
-// One thread per output 16-byte chunk.
-static __global__ __launch_bounds__(256) void p16t_pack_kernel(const uint8_t* __restrict__ w, int nrows, int nblk, int ldb, uint8_t* __restrict__ out) {
-    const int G = (nblk + 15) >> 4;
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)nrows * G * 16) return;
-    const int t = (int)(idx & 15);
-    const long long rg = idx >> 4;
-    const int g = (int)(rg % G);
-    const long long row = rg / G;
-    const uint8_t* src = w + (size_t)row * ldb + (size_t)g * 256 + t;
-    // where the chunk goes: the four rows of a row quad are INTERLEAVED per group -- [quad][group][row in quad][chunk t] -- so that the
-    // wave instruction of a quad (lane = 16 r + t) reads 1 KiB contiguous, like the T16 copies (round 5: as four 256-byte pieces 2 KB
-    // apart the LM head streamed at 4.4 TB/s against gate|up's 5.3, profiles/r05e_*)
-    const long long oidx = ((row >> 2) * G + g) * 64 + (row & 3) * 16 + t;
-    // dword d of the chunk = nibble pair t of blocks 4d..4d+3 (b0..b3), nibble positions (from bit 0):
-    //   [lo_b1, lo_b0, hi_b1, hi_b0, lo_b3, lo_b2, hi_b3, hi_b2]
-    // so that  x & 0xF0F0F0F0         = bytes [lo_b0, hi_b0, lo_b2, hi_b2] * 16  (one op)
-    //          (x << 4) & 0xF0F0F0F0  = bytes [lo_b1, hi_b1, lo_b3, hi_b3] * 16  (two ops)
-    // are the v_dot4 operands of the four blocks as they stand (against pair words placed in the low / high half): no byte shuffle
-    i32x4 v = {0, 0, 0, 0};
-#pragma unroll
-    for (int c = 0; c < 16; c++) {
-        const unsigned byte = (16 * g + c < nblk) ? (unsigned)src[c * 16] : 0u;
-        const unsigned lo = byte & 15u, hi = byte >> 4;
-        const int b = c & 3;
-        const int plo = (b == 0) ? 4 : (b == 1) ? 0 : (b == 2) ? 20 : 16;   // bit position of the low nibble; the high one sits 8 bits above
-        v[c >> 2] |= (int)((lo << plo) | (hi << (plo + 8)));
-    }
-    ((i32x4*)out)[oidx] = v;
-}
+// chunk t holds nibble pair t (elements t and t+16) of the group's 16 blocks, four blocks per dword; the rows of a quad interleaved per group.
+// Made by p16t_pack_kernel (model.hip), which spells out the row interleave and the nibble order.
 static inline size_t p16t_row_bytes(int K) { return (size_t)((K / QB + 15) / 16) * 256; }   // bytes per row; a quad's four rows share 4 of them, interleaved
 // 32-bit LDS byte address of a shared-memory pointer (operand of the asm ds_read forms below)
 __device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p; }

@@ -33,36 +33,7 @@ typedef float f32x4t __attribute__((ext_vector_type(4)));
 constexpr int T16_SEL_STRIDE = 136;   // bytes per block in the selector table: 16 x 8 B (the active lanes) + 8 zero bytes (everyone else)
 
 // ------------------------------------------------------------------------------------------------ packer
-// mode 0: tile u = rows 16u..16u+15 of w;  mode 1 (gate|up): tile u = rows 8u..8u+7 of w (gate) then 8u..8u+7 of w2 (up).
-// One thread per (tile, q, j): 64 contiguous bytes (4 blocks) of its row in, 4 x 16 bytes out (one per lane group).
-static __global__ __launch_bounds__(256) void t16_pack_kernel(const i32x4* __restrict__ w, const float* __restrict__ ws, const i32x4* __restrict__ w2,
-                                                       const float* __restrict__ ws2, int nblk, int ntiles, int mode, i32x4* __restrict__ tw,
-                                                       f32x4t* __restrict__ ts) {
-    const int nq = nblk >> 2;
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)ntiles * nq * 16) return;
-    const int j = (int)(idx & 15);
-    const long long uq = idx >> 4;
-    const int q = (int)(uq % nq), u = (int)(uq / nq);
-    const i32x4* src;
-    const float* ssrc;
-    if (mode == 1) {
-        const int row = 8 * u + (j & 7);
-        src = ((j < 8) ? w : w2) + (size_t)row * nblk;
-        ssrc = ((j < 8) ? ws : ws2) + (size_t)row * nblk;
-    } else {
-        const int row = 16 * u + j;
-        src = w + (size_t)row * nblk;
-        ssrc = ws + (size_t)row * nblk;
-    }
-    const i32x4 b0 = src[4 * q], b1 = src[4 * q + 1], b2 = src[4 * q + 2], b3 = src[4 * q + 3];
-    i32x4* dst = tw + (size_t)uq * 64 + j;
-    dst[0] = i32x4{b0.x, b1.x, b2.x, b3.x};
-    dst[16] = i32x4{b0.y, b1.y, b2.y, b3.y};
-    dst[32] = i32x4{b0.z, b1.z, b2.z, b3.z};
-    dst[48] = i32x4{b0.w, b1.w, b2.w, b3.w};
-    ts[(size_t)uq * 16 + j] = *(const f32x4t*)(ssrc + 4 * q);
-}
+// t16_pack_kernel (model.hip) makes the T16 copies; their sizes:
 static inline size_t t16_w_bytes(int rows, int K) { return (size_t)rows * (K / QB) * 16; }
 static inline size_t t16_s_bytes(int rows, int K) { return (size_t)rows * (K / QB) * 4; }
 

@@ -2,6 +2,74 @@
 #include "jh_host.h"
 #include "jh_launch.h"
 
+// ---- kernels of this unit: the sampler's exp / norm passes and the argmax / next-row step
+namespace jh {
+
+// temperature sampling (jh_kernels.h, sample_sum_kernel): v_i = (float)exp((logit_i - max) / T) in double, whole chip
+static __global__ __launch_bounds__(256) void sample_exp_kernel(const float* logits, int V, const float* partv, int nparts, float temperature, float* prob) {
+    __shared__ float red[4];
+    float m = -INFINITY;
+    for (int i = threadIdx.x; i < nparts; i += 256) m = fmaxf(m, partv[i]);   // the LM head's per-workgroup maxima
+    m = wave_max(m);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    const double maxv = (double)fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < V) prob[i] = (float)exp(((double)logits[i] - maxv) / (double)temperature);
+}
+static __global__ __launch_bounds__(256) void sample_norm_kernel(float* prob, int V, const DecodeState* st, const float* sum) {
+    if (st->done) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < V) prob[i] = prob[i] / *sum;                              // :481-483
+}
+// argmax over the LM head's per-workgroup partials -> next token; advance the decode state and look up the
+// next embedding row, so a greedy decode step needs no host round trip (AbstractModel.java:590-599).
+// Stop tokens (Config.eosTokens, AbstractModel.java:600-603): the step that samples one is the last; st->done freezes
+// the state, so the remaining replays of an already-queued decode loop emit nothing.
+static __global__ void finish_token_kernel(const float* partv, const int* parti, int nparts, DecodeState* st,
+                                    int* out_tokens, const void* table, const float* scales, int dtype, int E,
+                                    float* x, int do_embed, const int* eos,   // eos: [count, id0, id1, ...] (jh_session_set_eos)
+                                    const int* forced) {                      // non-null: the sampled id (sample_pick_kernel) replaces the argmax
+    __shared__ float sv[16];
+    __shared__ int si[16];
+    __shared__ int tok;
+    if (st->done) return;   // uniform: every thread reads the same word
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
+        const float v = partv[i];
+        const int id = parti[i];
+        if (v > bv || (v == bv && id < bi)) { bv = v; bi = id; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o);
+        const int oi = __shfl_xor(bi, o);
+        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    if (lane == 0) { sv[wave] = bv; si[wave] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 0; w < nw; w++)
+            if (sv[w] > bv || (sv[w] == bv && si[w] < bi)) { bv = sv[w]; bi = si[w]; }
+        if (forced) bi = *forced;
+        tok = bi;
+        out_tokens[st->step] = bi;
+        st->token = bi;
+        st->pos = st->pos + 1;
+        st->step = st->step + 1;
+        int stop = 0;
+        const int n_eos = eos[0];
+        for (int i = 0; i < n_eos; i++) stop |= (eos[1 + i] == bi);
+        st->done = stop;
+    }
+    __syncthreads();
+    if (do_embed) embed_row(table, scales, dtype, tok, E, x);
+}
+
+}  // namespace jh
+
 int attn_launch(jh_session* s, int rel, hipStream_t st, bool tap, long long* dbg) {
     jh_model* m = s->m;
     const jh_config& c = m->c;

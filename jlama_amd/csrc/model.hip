@@ -2,6 +2,94 @@
 #include "jh_host.h"
 #include "jh_launch.h"
 
+// ---- kernels of this unit: the operand pack kernels (T16 / P16T / BF16T copies) and the BF16 widening
+namespace jh {
+
+static __global__ void widen_bf16_kernel(const uint16_t* in, long long n, float* out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = bf16_to_f32(in[i]);
+}
+// T16 copy (jh_t16.h).  mode 0: tile u = rows 16u..16u+15 of w;  mode 1 (gate|up): tile u = rows 8u..8u+7 of w (gate) then
+// 8u..8u+7 of w2 (up).  One thread per (tile, q, j): 64 contiguous bytes (4 blocks) of its row in, 4 x 16 bytes out (one per lane group).
+static __global__ __launch_bounds__(256) void t16_pack_kernel(const i32x4* __restrict__ w, const float* __restrict__ ws, const i32x4* __restrict__ w2,
+                                                       const float* __restrict__ ws2, int nblk, int ntiles, int mode, i32x4* __restrict__ tw,
+                                                       f32x4t* __restrict__ ts) {
+    const int nq = nblk >> 2;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)ntiles * nq * 16) return;
+    const int j = (int)(idx & 15);
+    const long long uq = idx >> 4;
+    const int q = (int)(uq % nq), u = (int)(uq / nq);
+    const i32x4* src;
+    const float* ssrc;
+    if (mode == 1) {
+        const int row = 8 * u + (j & 7);
+        src = ((j < 8) ? w : w2) + (size_t)row * nblk;
+        ssrc = ((j < 8) ? ws : ws2) + (size_t)row * nblk;
+    } else {
+        const int row = 16 * u + j;
+        src = w + (size_t)row * nblk;
+        ssrc = ws + (size_t)row * nblk;
+    }
+    const i32x4 b0 = src[4 * q], b1 = src[4 * q + 1], b2 = src[4 * q + 2], b3 = src[4 * q + 3];
+    i32x4* dst = tw + (size_t)uq * 64 + j;
+    dst[0] = i32x4{b0.x, b1.x, b2.x, b3.x};
+    dst[16] = i32x4{b0.y, b1.y, b2.y, b3.y};
+    dst[32] = i32x4{b0.z, b1.z, b2.z, b3.z};
+    dst[48] = i32x4{b0.w, b1.w, b2.w, b3.w};
+    ts[(size_t)uq * 16 + j] = *(const f32x4t*)(ssrc + 4 * q);
+}
+// P16T copy of a Q4 weight (jh_p16.h): one thread per output 16-byte chunk
+static __global__ __launch_bounds__(256) void p16t_pack_kernel(const uint8_t* __restrict__ w, int nrows, int nblk, int ldb, uint8_t* __restrict__ out) {
+    const int G = (nblk + 15) >> 4;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)nrows * G * 16) return;
+    const int t = (int)(idx & 15);
+    const long long rg = idx >> 4;
+    const int g = (int)(rg % G);
+    const long long row = rg / G;
+    const uint8_t* src = w + (size_t)row * ldb + (size_t)g * 256 + t;
+    // where the chunk goes: the four rows of a row quad are INTERLEAVED per group -- [quad][group][row in quad][chunk t] -- so that the
+    // wave instruction of a quad (lane = 16 r + t) reads 1 KiB contiguous, like the T16 copies (round 5: as four 256-byte pieces 2 KB
+    // apart the LM head streamed at 4.4 TB/s against gate|up's 5.3, profiles/r05e_*)
+    const long long oidx = ((row >> 2) * G + g) * 64 + (row & 3) * 16 + t;
+    // dword d of the chunk = nibble pair t of blocks 4d..4d+3 (b0..b3), nibble positions (from bit 0):
+    //   [lo_b1, lo_b0, hi_b1, hi_b0, lo_b3, lo_b2, hi_b3, hi_b2]
+    // so that  x & 0xF0F0F0F0         = bytes [lo_b0, hi_b0, lo_b2, hi_b2] * 16  (one op)
+    //          (x << 4) & 0xF0F0F0F0  = bytes [lo_b1, hi_b1, lo_b3, hi_b3] * 16  (two ops)
+    // are the v_dot4 operands of the four blocks as they stand (against pair words placed in the low / high half): no byte shuffle
+    i32x4 v = {0, 0, 0, 0};
+#pragma unroll
+    for (int c = 0; c < 16; c++) {
+        const unsigned byte = (16 * g + c < nblk) ? (unsigned)src[c * 16] : 0u;
+        const unsigned lo = byte & 15u, hi = byte >> 4;
+        const int b = c & 3;
+        const int plo = (b == 0) ? 4 : (b == 1) ? 0 : (b == 2) ? 20 : 16;   // bit position of the low nibble; the high one sits 8 bits above
+        v[c >> 2] |= (int)((lo << plo) | (hi << (plo + 8)));
+    }
+    ((i32x4*)out)[oidx] = v;
+}
+// BF16T copy of a row-major BF16 weight [nrows, ldw elements] (jh_bf16r.h): one thread per output 16-byte chunk
+static __global__ __launch_bounds__(256) void bf16t_pack_kernel(const uint16_t* __restrict__ w, int nrows, int K, int ldw, uint8_t* __restrict__ out) {
+    const int G = (K + BF16R_GROUP - 1) / BF16R_GROUP;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)nrows * G * 16) return;
+    const int t = (int)(idx & 15);
+    const long long rg = idx >> 4;
+    const int g = (int)(rg % G);
+    const long long row = rg / G;
+    const uint16_t* src = w + (size_t)row * ldw + (size_t)g * BF16R_GROUP;
+    i32x4 v = {0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int e = g * BF16R_GROUP + 32 * i;
+        if (e < K) v[i] = (int)((unsigned)src[32 * i + t] | ((unsigned)src[32 * i + 16 + t] << 16));
+    }
+    ((i32x4*)out)[((row >> 2) * G + g) * 64 + (row & 3) * 16 + t] = v;   // the rows of a quad interleaved per group, as in the P16T copies (jh_p16.h)
+}
+
+}  // namespace jh
+
 bool is_global_slot(int which) { return which == JH_W_EMBED || which == JH_W_LMHEAD || which == JH_W_FINALNORM; }
 
 thread_local int g_operand_packs = 0;   // operand copies this thread has queued a pack kernel for (ensure_strict_operands waits for them)

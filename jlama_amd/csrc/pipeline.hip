@@ -2,6 +2,21 @@
 #include "jh_host.h"
 #include "jh_launch.h"
 
+// ---- kernels of this unit: decode-state setters of the pipeline stages (other units: the launcher below)
+namespace jh {
+
+static __global__ void set_pos_kernel(DecodeState* st, int pos) { st->pos = pos; }   // pipeline stages: the token / step words stay
+// one pipeline stage per process: the token id arrives in device memory (shipped by the last stage), never through the host
+static __global__ void set_state_dev_kernel(DecodeState* st, int pos, const int* token_dev) {
+    st->pos = pos; st->step = 0; st->done = 0;
+    if (token_dev) st->token = *token_dev;
+}
+static __global__ void store_token_kernel(const DecodeState* st, int* out) { *out = st->token; }
+
+}  // namespace jh
+
+void launch_set_pos(DecodeState* d, int pos, hipStream_t st) { hipLaunchKernelGGL(set_pos_kernel, dim3(1), dim3(1), 0, st, d, pos); }
+
 extern "C" {
 
 // ---- one-process layer-sharded pipeline ------------------------------------------------------------------------------
@@ -130,9 +145,9 @@ int jh_pipeline_decode_n_async(jh_pipeline* p, int32_t first_token, int start_po
         }
     }
     HIPCHK(hipSetDevice(s0->m->device));
-    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, s0->stream, s0->st, start_pos, first_token, 0);
+    launch_set_state(s0->st, start_pos, first_token, s0->stream);
     HIPCHK(hipSetDevice(sl->m->device));
-    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, sl->stream, sl->st, start_pos, first_token, 0);
+    launch_set_state(sl->st, start_pos, first_token, sl->stream);
     HIPCHK(hipEventRecord(sl->ev0, sl->stream));
     for (int i = 0; i < n; i++) {
         const int pos = start_pos + i;
@@ -146,15 +161,14 @@ int jh_pipeline_decode_n_async(jh_pipeline* p, int32_t first_token, int start_po
                     HIPCHK(hipStreamWaitEvent(st, p->done[N - 1], 0));
                     HIPCHK(hipMemcpyPeerAsync(&s->st->token, s->m->device, &sl->st->token, sl->m->device, sizeof(int), st));
                 }
-                hipLaunchKernelGGL(set_pos_kernel, dim3(1), dim3(1), 0, st, s->st, pos);
-                hipLaunchKernelGGL(embed_kernel, dim3(1), dim3(256), 0, st, (const void*)emb.data, (const float*)emb.scales, emb.dtype,
-                                   (const DecodeState*)s->st, (int)E, s->x);
+                launch_set_pos(s->st, pos, st);
+                launch_embed(emb, s->st, (int)E, s->x, st);
                 HIPCHK(hipGetLastError());
                 HIPCHK(hipGraphLaunch(s->row_exec[v], st));
             } else {
                 HIPCHK(hipStreamWaitEvent(st, p->done[k - 1], 0));
                 HIPCHK(hipMemcpyPeerAsync(s->x, s->m->device, p->st[k - 1]->x, p->st[k - 1]->m->device, E * 4, st));
-                hipLaunchKernelGGL(set_pos_kernel, dim3(1), dim3(1), 0, st, s->st, pos);
+                launch_set_pos(s->st, pos, st);
                 HIPCHK(hipGetLastError());
                 HIPCHK(hipGraphLaunch(k == N - 1 ? s->exec[v] : s->row_exec[v], st));   // last stage: layers + LM head + argmax
             }
@@ -200,8 +214,7 @@ int jh_stage_decode_async(jh_session* s, const int32_t* token_dev, const float* 
     else JHCHK(build_row_graph(s, v));
     hipLaunchKernelGGL(set_state_dev_kernel, dim3(1), dim3(1), 0, st, s->st, pos, first ? token_dev : nullptr);
     if (first)
-        hipLaunchKernelGGL(embed_kernel, dim3(1), dim3(256), 0, st, (const void*)emb.data, (const float*)emb.scales, emb.dtype,
-                           (const DecodeState*)s->st, (int)E, s->x);
+        launch_embed(emb, s->st, (int)E, s->x, st);
     else
         HIPCHK(hipMemcpyAsync(s->x, x_in_dev, E * 4, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipGetLastError());

@@ -2,6 +2,103 @@
 #include "jh_host.h"
 #include "jh_launch.h"
 
+// ---- kernels of this unit: operand re-tiling, embedding rows, RoPE + KV writes and the split combine of a prompt chunk (other units: the launchers below)
+namespace jh {
+
+static __global__ void set_int_kernel(int* p, int v) { *p = v; }
+// Re-tile a row-major weight into MFMA order for the prefill GEMMs:
+//   Q4   [N][K/2] (+ scales [N][K/32])  ->  wt [N/32][K/32][32 rows][16 B],  st [N/32][K/32][32]
+//   BF16 [N][K]                         ->  wt [N/32][K/16][h][32 rows][8 values]
+// At streaming rate, for both weight types (it also runs in front of every prefill GEMM when the MFMA-ordered copy is NOT kept
+// resident, JH_TILED_COPY=transient):  a weight row is `nch` 16-byte chunks (Q4: one block of 32 nibbles; BF16: 8 values --
+// the [k slice][h] pair is chunk index c8 = 2*ksl + h, so both layouts are dst = ((panel*nch + chunk)*32 + row)*16 B), the
+// destination is [N/32][nch][32 rows][16 B] (+ Q4 scales [N/32][nch][32]).  One workgroup moves a 32-row x 64-chunk tile
+// through LDS: reads are 1 KiB contiguous per wave (a row's 64 chunks), writes 1 KiB contiguous per wave (2 chunks x 32 rows).
+// LDS rows are padded by one chunk so that the transposed ds_read_b128 (32 lanes = 32 rows of one chunk) is conflict-free.
+static __global__ __launch_bounds__(256) void retile16_kernel(const i32x4* __restrict__ w, const float* __restrict__ ws, int N, int nch,
+                                                       i32x4* __restrict__ wt, float* __restrict__ st) {
+    __shared__ i32x4 tile[32 * 65];
+    __shared__ float stile[32 * 65];
+    const int panel = blockIdx.y, c0 = blockIdx.x * 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int cin = c0 + lane;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const int r = wave + 4 * i;
+        if (cin < nch) {
+            const size_t src = (size_t)(panel * 32 + r) * nch + cin;
+            tile[r * 65 + lane] = __builtin_nontemporal_load(w + src);
+            if (ws) stile[r * 65 + lane] = __builtin_nontemporal_load(ws + src);
+        }
+    }
+    __syncthreads();
+    const int row = lane & 31, hh = lane >> 5;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const int cl = 2 * (wave + 4 * i) + hh;        // chunk within the tile
+        if (c0 + cl < nch) {
+            const size_t dst = ((size_t)panel * nch + c0 + cl) * 32 + row;
+            wt[dst] = tile[row * 65 + cl];
+            if (ws) st[dst] = stile[row * 65 + cl];
+        }
+    }
+}
+static __global__ void embed_rows_kernel(const void* table, const float* scales, int dtype, const int* tokens, int E, float* x) {
+    embed_row(table, scales, dtype, tokens[blockIdx.x], E, x + (size_t)blockIdx.x * E);
+}
+// RoPE of q (in place) and k, and the KV page writes, for every row of the chunk (CausalSelfAttention.java:199-286;
+// the table offset is position*half + kvHead*headSize for q and k alike -- SURVEY.md 8a "RoPE quirk").
+static __global__ __launch_bounds__(256) void rows_rope_kv_kernel(PrefillAttnParams p) {
+    const int row = blockIdx.x, pos = p.start_pos[0] + row;
+    const int HS = p.head_size, half = HS / 2, A = p.n_heads * HS, KV = p.n_kv_heads * HS, group = p.n_heads / p.n_kv_heads;
+    float* r = p.qkv + (size_t)row * p.ldqkv;
+    float* krow = (float*)kv_row(p, 0, pos, KV);
+    float* vrow = (float*)kv_row(p, 1, pos, KV);
+    const int npairs = (p.n_heads + p.n_kv_heads) * half;
+    const int t0 = blockIdx.y * blockDim.x + threadIdx.x, tstep = blockDim.x * gridDim.y;   // gridDim.y workgroups per row
+    for (int i = t0; i < npairs; i += tstep) {
+        const int hh = i / half, d = i - hh * half;
+        const bool isq = hh < p.n_heads;
+        const int kvh = isq ? hh / group : hh - p.n_heads;
+        const float* rf = p.rope + ((size_t)pos * half + (size_t)(kvh + p.kv_head_offset) * HS) * 2;
+        float* v = isq ? r + (size_t)hh * HS : r + A + (size_t)kvh * HS;
+        const float a = v[d], b = v[d + half], c = rf[2 * d], s = rf[2 * d + 1];
+        const float r0 = a * c - b * s;
+        const float r1 = a * s + b * c;
+        if (isq) { v[d] = r0; v[d + half] = r1; }
+        else { krow[(size_t)kvh * HS + d] = r0; krow[(size_t)kvh * HS + d + half] = r1; }
+    }
+    for (int i = t0; i < KV; i += tstep) vrow[i] = r[A + KV + i];
+}
+// merge the key-range splits of attn_prefill_mfma_kernel: w_s = exp(m_s - M), out = sum_s w_s O_s / sum_s w_s l_s (split order)
+static __global__ __launch_bounds__(128) void attn_prefill_combine_kernel(PrefillAttnParams p, PrefillMfmaExtra e) {
+    const int row = blockIdx.x, head = blockIdx.y, HS = p.head_size;
+    const float* ml = e.ws_ml + ((size_t)row * p.n_heads + head) * e.nsplit * 2;
+    float M = -INFINITY;
+    for (int s = 0; s < e.nsplit; s++) M = fmaxf(M, ml[2 * s]);
+    float L = 0.0f;
+    for (int s = 0; s < e.nsplit; s++) {
+        const float w = ml[2 * s] == -INFINITY ? 0.0f : (float)exp((double)(ml[2 * s] - M));
+        L += ml[2 * s + 1] * w;
+    }
+    const float* ob = e.ws_o + ((size_t)row * p.n_heads + head) * e.nsplit * HS;
+    for (int d = threadIdx.x; d < HS; d += blockDim.x) {
+        float o = 0.0f;
+        for (int s = 0; s < e.nsplit; s++) {
+            const float w = ml[2 * s] == -INFINITY ? 0.0f : (float)exp((double)(ml[2 * s] - M));
+            o = fmaf(ob[(size_t)s * HS + d], w, o);
+        }
+        p.out[(size_t)row * p.ldo + (size_t)head * HS + d] = o / L;
+    }
+}
+
+}  // namespace jh
+
+void launch_set_int(int* p, int v, hipStream_t st) { hipLaunchKernelGGL(set_int_kernel, dim3(1), dim3(1), 0, st, p, v); }
+void launch_embed_rows(const JWeight& emb, const int* tokens, int rows, int E, float* x, hipStream_t st) {
+    hipLaunchKernelGGL(embed_rows_kernel, dim3(rows), dim3(256), 0, st, (const void*)emb.data, (const float*)emb.scales, emb.dtype, tokens, E, x);
+}
+
 // ---- batched prefill -----------------------------------------------------------------------------------------------
 
 // reference-order sessions: prompt rows through the M-row p16 GEMM (jh_p16.h) -- whole groups of 16 Q blocks in every K
@@ -636,13 +733,12 @@ int prefill_chunk(jh_session* s, const int32_t* tokens, const float* x_in, bool 
     if (tokens) {
         const JWeight& emb = m->global_w[JH_W_EMBED];
         HIPCHK(hipMemcpyAsync(s->pb_tok, tokens, (size_t)rows * 4, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(embed_rows_kernel, dim3(rows), dim3(256), 0, st, (const void*)emb.data, (const float*)emb.scales, emb.dtype,
-                           (const int*)s->pb_tok, E, s->pb_x);
+        launch_embed_rows(emb, s->pb_tok, rows, E, s->pb_x, st);
         HIPCHK(hipGetLastError());
     } else {
         HIPCHK(hipMemcpyAsync(s->pb_x, x_in, (size_t)rows * E * 4, x_in_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     }
-    hipLaunchKernelGGL(set_int_kernel, dim3(1), dim3(1), 0, st, s->pb_start, start_pos);
+    launch_set_int(s->pb_start, start_pos, st);
     HIPCHK(hipGetLastError());
     // ~15 launches per layer, many of them 5 us kernels: replay a captured graph of the layer loop.  The graph depends on
     // the chunk's row count (grids) and on an LDS bound for the score rows, not on the position: every full 256-row chunk
@@ -677,7 +773,7 @@ int prefill_chunk(jh_session* s, const int32_t* tokens, const float* x_in, bool 
     }
     // the chunk's last row is the session's current row (what sample() / the next shard's hand-off reads)
     HIPCHK(hipMemcpyAsync(s->x, s->pb_x + (size_t)(rows - 1) * E, (size_t)E * 4, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, s->st, start_pos + rows - 1, tokens ? tokens[rows - 1] : 0, 0);
+    launch_set_state(s->st, start_pos + rows - 1, tokens ? tokens[rows - 1] : 0, st);
     if (x_out)
         HIPCHK(hipMemcpyAsync(x_out, s->pb_x, (size_t)rows * E * 4, x_out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
     return JH_OK;

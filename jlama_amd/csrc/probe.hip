@@ -14,7 +14,7 @@ int jh_debug_attn_timeline(jh_session* s, int pos, long long* out, int n) {
     HIPCHK(hipMemset(d, 0xff, 256 * 8));
     hipStream_t st = s->stream;
     for (int it = 0; it < 3; it++) {   // warm: the last launch's stamps are the ones reported
-        hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, s->st, pos, 0, 0);
+        launch_set_state(s->st, pos, 0, st);
         s->attn_variant = attn_variant_for(s, pos);
         JHCHK(attn_launch(s, 0, st, false, d));
     }
@@ -107,7 +107,7 @@ int jh_kernel_bench(jh_session* s, int which, int iters, double* out_ms, int64_t
     const int nl = c.layer_end - c.layer_start;
     JHCHK(ensure_strict_operands(s, st));
     JHCHK(refuse_order_free(s, "kernel_bench"));
-    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, s->st, s->max_ctx / 2, 0, 0);
+    launch_set_state(s->st, s->max_ctx / 2, 0, st);
     s->attn_variant = attn_variant_for(s, s->max_ctx / 2);
     const bool p16 = s->strict != 0;   // reference-order kernels (jh_t16.h / jh_p16.h) when the session is in that mode
     int launches = 0;

@@ -2,6 +2,148 @@
 #include "jh_host.h"
 #include "jh_launch.h"
 
+// ---- kernels of this unit: the Tier-1 elementwise, norm, quantize and RoPE kernels
+namespace jh {
+
+static __global__ void acc_q4_kernel(float* a, const uint8_t* nib, const float* sc, int offset, int n) {
+    const int i = offset + blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= offset + n) return;
+    const int blk = i / 32, in = i % 32;
+    const uint8_t b = nib[blk * 16 + (in & 15)];
+    const int x = (in < 16) ? (b & 0x0F) - 8 : ((b >> 4) & 0x0F) - 8;
+    a[i] = a[i] + (float)x * sc[blk];
+}
+// batched saxpy: thread per element, fma chain over rows in ascending order (PTO:2648-2698)
+static __global__ void saxpy_batch_kernel(const float* alpha, const float* x, int ldx, float* y, int limit, int rows) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= limit) return;
+    float acc = y[t];
+    for (int n = 0; n < rows; n++) acc = fmaf(x[(size_t)n * ldx + t], alpha[n], acc);
+    y[t] = acc;
+}
+// quantize F32 -> I8 (PTO:1684-1723): one 32-lane half-wave per block
+static __global__ void quantize_q8_kernel(const float* x, int rows, int ldx, int offset, int length, int8_t* q, int ldq,
+                                   float* d, int ldd) {
+    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+    const int hw = gid >> 5, l = gid & 31;
+    const int bpr = length / QB;
+    if (hw >= rows * bpr) return;
+    const int r = hw / bpr, blk = hw % bpr;
+    const int e = offset + blk * QB + l;
+    const float y = x[(size_t)r * ldx + e];
+    float amax = fabsf(y);
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
+    const float dd = amax / 127.0f;
+    const float id = (amax != 0.0f) ? 127.0f / amax : 0.0f;
+    float v = y * id;
+    v = v + 0.5f;
+    q[(size_t)r * ldq + e] = (int8_t)f2b(v);
+    if (l == 0) d[(size_t)r * ldd + e / QB] = dd;
+}
+static __global__ void quantize_bf16_kernel(const float* x, long long n, uint16_t* out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = f32_to_bf16(x[i]);
+}
+// BF16 result tensor of a Tier-1 GEMM: out[i*ld + j] = bf16(in[i*ld + j]) for j < n, one grid row per matrix row
+static __global__ void store_bf16_2d_kernel(const float* in, uint16_t* out, int n, int ld) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) out[(size_t)blockIdx.y * ld + j] = f32_to_bf16(in[(size_t)blockIdx.y * ld + j]);
+}
+// RMSNorm.forward (core/model/RMSNorm.java:33-56), single workgroup per row
+static __global__ __launch_bounds__(1024) void rmsnorm_kernel(const float* x, const float* w, float adj, int n, float eps,
+                                                       float* out) {
+    __shared__ double red[32];
+    double ss = 0.0;
+    for (int j = threadIdx.x; j < n; j += blockDim.x) { const float v = x[j]; ss += (double)(v * v); }
+    ss = block_sum_d(ss, red);
+    ss /= (double)n;
+    ss += (double)eps;
+    ss = 1.0 / sqrt(ss);
+    const float fs = (float)ss;
+    for (int j = threadIdx.x; j < n; j += blockDim.x) out[j] = (adj + w[j]) * (fs * x[j]);
+}
+// LayerNorm.forward (core/model/LayerNorm.java:41-67), GPT-2's norm: FLOAT sums accumulated in index order (one lane
+// walks the row so the running sums round exactly as the Java loop's), var = sumSq/E - mean^2,
+// 1/(float)sqrt(var+eps), then ((x-mean)*inv)*w + b with no fused multiply-add.  One wave per row.
+static __global__ __launch_bounds__(64) void layernorm_kernel(const float* x, const float* w, const float* b, int ld, int offset, int length,
+                                                       int divisor, float eps, float* out) {
+    const float* row = x + (size_t)blockIdx.x * ld;
+    float* orow = out + (size_t)blockIdx.x * ld;
+    __shared__ float stats[2];
+    if (threadIdx.x == 0) {
+        float sum = 0.0f, sumsq = 0.0f;
+        for (int i = offset; i < offset + length; i++) {
+            const float v = row[i];
+            sum += v;
+            sumsq += v * v;
+        }
+        const float mean = sum / (float)divisor;
+        const float variance = sumsq / (float)divisor - mean * mean;
+        stats[0] = mean;
+        stats[1] = 1.0f / (float)sqrt((double)(variance + eps));
+    }
+    __syncthreads();
+    const float mean = stats[0], inv = stats[1];
+    for (int i = offset + threadIdx.x; i < offset + length; i += blockDim.x) orow[i] = (row[i] - mean) * inv * w[i] + b[i];
+}
+// ActivationFunction.eval GELU (core/math/ActivationFunction.java:32-34): tanh approximation evaluated in double
+static __global__ void gelu_kernel(float* x, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double v = (double)x[i];
+    x[i] = (float)(0.5 * v * (1.0 + tanh(sqrt(2.0 / 3.14159265358979323846) * (v + 0.044715 * pow(v, 3.0)))));
+}
+// VectorMath.softMax (core/math/VectorMath.java:69-90), single workgroup
+static __global__ __launch_bounds__(1024) void softmax_kernel(float* x, int offset, int length) {
+    __shared__ float redf[32];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    float m = -INFINITY;
+    for (int i = offset + threadIdx.x; i < offset + length; i += blockDim.x) m = fmaxf(m, x[i]);
+    m = wave_max(m);
+    if (lane == 0) redf[wave] = m;
+    __syncthreads();
+    m = redf[0];
+    for (int i = 1; i < nw; i++) m = fmaxf(m, redf[i]);
+    __syncthreads();
+    float s = 0.0f;
+    for (int i = offset + threadIdx.x; i < offset + length; i += blockDim.x) {
+        const float e = (float)exp((double)(x[i] - m));
+        x[i] = e;
+        s += e;
+    }
+    s = wave_sum(s);
+    if (lane == 0) redf[wave] = s;
+    __syncthreads();
+    s = 0.0f;
+    for (int i = 0; i < nw; i++) s += redf[i];
+    for (int i = threadIdx.x; i < offset + length; i += blockDim.x) x[i] = x[i] / s;  // reference divides from index 0
+}
+// RoPE rotation, GQA branch (core/model/CausalSelfAttention.java:247-286)
+static __global__ void rope_kernel(float* q, float* k, const float* rope, int position, int n_heads, int n_kv_heads, int hs) {
+    const int half = hs / 2, group = n_heads / n_kv_heads;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int poffset = position * half;
+    if (i < n_heads * half) {
+        const int h = i / half, d = i % half;
+        const int g = (h / group) * hs + d;
+        const float fcr = rope[(size_t)(poffset + g) * 2], fci = rope[(size_t)(poffset + g) * 2 + 1];
+        const float q0 = q[h * hs + d], q1 = q[h * hs + d + half];
+        q[h * hs + d] = q0 * fcr - q1 * fci;
+        q[h * hs + d + half] = q0 * fci + q1 * fcr;
+    } else if (i < (n_heads + n_kv_heads) * half) {
+        const int ii = i - n_heads * half;
+        const int h = ii / half, d = ii % half;
+        const int g = h * hs + d;
+        const float fcr = rope[(size_t)(poffset + g) * 2], fci = rope[(size_t)(poffset + g) * 2 + 1];
+        const float k0 = k[h * hs + d], k1 = k[h * hs + d + half];
+        k[h * hs + d] = k0 * fcr - k1 * fci;
+        k[h * hs + d + half] = k0 * fci + k1 * fcr;
+    }
+}
+
+}  // namespace jh
+
 namespace {
 // Shared Tier-1 GEMM driver.  a_es/b_es: element size in bytes of A / B storage rows (Q4: ldb already in bytes).
 int tier1_gemm(int kind, int64_t b_id, int64_t bf_id, const void* a, const float* af, int aoffset, const void* b,

@@ -2,6 +2,101 @@
 #include "jh_host.h"
 #include "jh_launch.h"
 
+// ---- kernels of this unit: the tensor-parallel reductions and token hand-over
+namespace jh {
+
+static __global__ void add_rows_kernel(const float* a, const float* b, float* out, int n) {   // out = a + b (residual add)
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = a[i] + b[i];
+}
+// tensor-parallel one-shot reduction: a shard's partial [E] goes straight into its slot of EVERY shard's
+// slot buffer (peer stores over xGMI when the destination lives on another device) ...
+static __global__ void tp_scatter_kernel(const float* part, float* const* dst, int n_dst, int E) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= E) return;
+    const float v = part[i];
+    for (int j = 0; j < n_dst; j++) dst[j][i] = v;
+}
+// ... and every shard sums the N slots locally, in shard order 0..N-1 (the lock-step order: results never depend on which
+// peer arrived first)
+static __global__ void tp_sum_kernel(const float* slots, int n, int E, float* out, size_t stride) {   // stride: floats between two shards' slots
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= E) return;
+    float v = slots[i];
+    for (int k = 1; k < n; k++) v = v + slots[k * stride + i];
+    out[i] = v;
+}
+// the same reduction inside the group's token graph (jh_kernels.h: TPMail, tp_wait_ge): scatter + flags, wait + sum
+static __global__ __launch_bounds__(256) void tp_scatter_flag_kernel(const float* part, float* const* dst, unsigned* const* fdst, int n_dst, int E,
+                                                              const unsigned* seqp, int li, int L) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < E) {
+        const float v = part[i];
+        for (int j = 0; j < n_dst; j++) st_sys(dst[j] + i, v);
+    }
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned seq = *seqp * (unsigned)L + (unsigned)li + 1u;
+        for (int j = 0; j < n_dst; j++) __hip_atomic_store(fdst[j] + blockIdx.x, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+static __global__ __launch_bounds__(256) void tp_sum_wait_kernel(const float* slots, const unsigned* flags, int n, int E, int nwg, unsigned* seqp,
+                                                          int li, int L, const float* resid, float* out) {
+    const unsigned seq = *seqp * (unsigned)L + (unsigned)li + 1u;
+    if ((int)threadIdx.x < n) tp_wait_ge(flags + (size_t)threadIdx.x * nwg + blockIdx.x, seq, seqp + 1);
+    __syncthreads();
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= E) return;
+    float v = ld_sys(slots + i);
+    for (int k = 1; k < n; k++) v = v + ld_sys(slots + (size_t)k * E + i);   // shard order: the lock-step order
+    out[i] = resid[i] + v;                                                      // TransformerBlock.java:185 / :203
+}
+// the same meeting when the producers were the o-proj / down GEMVs themselves (GemvParams::tp_*): their workgroups own row ranges
+// that depend on the launch plan, so every consumer workgroup waits for ALL nflags workgroup flags of the N producers (a few
+// hundred words polled by 16 workgroups -- not the 256 x 256 of a grid barrier)
+static __global__ __launch_bounds__(256) void tp_sum_wait_all_kernel(const float* slots, const unsigned* flags, int n, int E, int nflags, int stride,
+                                                              unsigned* seqp, int li, int L, const float* resid, float* out) {
+    const unsigned seq = *seqp * (unsigned)L + (unsigned)li + 1u;
+    {   // a thread's flags are polled TOGETHER (independent loads, one memory round trip per sweep), bounded like tp_wait_ge
+        const long long t0 = wall_clock64();
+        unsigned* err = seqp + 1;
+        for (;;) {
+            bool all = true;
+            for (int i = threadIdx.x; i < n * nflags; i += 256)
+                all &= __hip_atomic_load(flags + (size_t)(i / nflags) * stride + (i % nflags), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) >= seq;
+            if (all) break;
+            if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
+            if (wall_clock64() - t0 > tp_wait_bound(err)) { __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
+            __builtin_amdgcn_s_sleep(2);
+        }
+    }
+    __syncthreads();
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= E) return;
+    float v = ld_sys(slots + i);
+    for (int k = 1; k < n; k++) v = v + ld_sys(slots + (size_t)k * E + i);   // shard order: the lock-step order
+    out[i] = resid[i] + v;                                                      // TransformerBlock.java:185 / :203
+}
+// shard 0, after finish_token_kernel: the next row (token, position) to every other shard's mailbox
+static __global__ void tp_publish_token_kernel(const DecodeState* st, TPMail* const* mails, int n, const unsigned* seqp) {
+    if (threadIdx.x >= (unsigned)n) return;
+    TPMail* m = mails[threadIdx.x];
+    __hip_atomic_store(&m->token, st->token, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&m->pos, st->pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __threadfence_system();
+    __hip_atomic_store(&m->seq, *seqp + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// the other shards, first node of their token graph: wait for the row of this replay, take it over
+static __global__ void tp_wait_token_kernel(const TPMail* mail, unsigned* seqp, DecodeState* st) {
+    tp_wait_ge(&mail->seq, *seqp, seqp + 1);
+    st->token = __hip_atomic_load(&mail->token, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    st->pos = __hip_atomic_load(&mail->pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+static __global__ void tp_bump_seq_kernel(unsigned* seqp) { *seqp = *seqp + 1u; }
+
+}  // namespace jh
+
 extern "C" {
 
 // ---- tensor-parallel (head-split) shard: the model is created with its LOCAL head counts / hidden length and holds
@@ -25,15 +120,14 @@ int jh_tp_set_row(jh_session* s, int32_t token, const float* x_dev, int pos) {
     hipStream_t st = s->stream;
     const int E = m->c.embedding_length;
     s->attn_variant = attn_variant_for(s, pos);
-    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, s->st, pos, token >= 0 ? token : 0, 0);
+    launch_set_state(s->st, pos, token >= 0 ? token : 0, st);
     if (x_dev) {
         HIPCHK(hipMemcpyAsync(s->x, x_dev, (size_t)E * 4, hipMemcpyDeviceToDevice, st));
     } else {
         const JWeight& emb = m->global_w[JH_W_EMBED];
         if (!emb.data) return set_err(JH_ERR_INVALID, "tp_set_row: this shard has no embedding table");
         if (token < 0 || token >= m->c.vocab_size) return set_err(JH_ERR_INVALID, "tp_set_row: token id out of range");
-        hipLaunchKernelGGL(embed_kernel, dim3(1), dim3(256), 0, st, (const void*)emb.data, (const float*)emb.scales, emb.dtype,
-                           (const DecodeState*)s->st, E, s->x);
+        launch_embed(emb, s->st, E, s->x, st);
     }
     HIPCHK(hipGetLastError());
     return JH_OK;
@@ -91,12 +185,11 @@ int jh_tp_set_rows(jh_session* s, const int32_t* tokens, const float* x_dev, int
     const int E = m->c.embedding_length;
     if (tokens) {
         HIPCHK(hipMemcpyAsync(s->pb_tok, tokens, (size_t)n * 4, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(embed_rows_kernel, dim3(n), dim3(256), 0, st, (const void*)emb.data, (const float*)emb.scales, emb.dtype,
-                           (const int*)s->pb_tok, E, s->pb_x);
+        launch_embed_rows(emb, s->pb_tok, n, E, s->pb_x, st);
     } else {
         HIPCHK(hipMemcpyAsync(s->pb_x, x_dev, (size_t)n * E * 4, hipMemcpyDeviceToDevice, st));
     }
-    hipLaunchKernelGGL(set_int_kernel, dim3(1), dim3(1), 0, st, s->pb_start, start_pos);
+    launch_set_int(s->pb_start, start_pos, st);
     HIPCHK(hipGetLastError());
     s->tp_rows = n;
     s->tp_pos0 = start_pos;
@@ -143,7 +236,7 @@ int jh_tp_finish_rows(jh_session* s, float* rows_out_dev) {
     const int E = s->m->c.embedding_length, rows = s->tp_rows;
     hipStream_t st = s->stream;
     HIPCHK(hipMemcpyAsync(s->x, s->pb_x + (size_t)(rows - 1) * E, (size_t)E * 4, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, s->st, s->tp_pos0 + rows - 1, s->tp_last_token, 0);
+    launch_set_state(s->st, s->tp_pos0 + rows - 1, s->tp_last_token, st);
     if (rows_out_dev) HIPCHK(hipMemcpyAsync(rows_out_dev, s->pb_x, (size_t)rows * E * 4, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipGetLastError());
     s->tp_rows = 0;
@@ -423,8 +516,7 @@ int tp_build_graph(jh_tp_group* g, int k, int v) {
     if (k > 0) {
         const JWeight& emb = s->m->global_w[JH_W_EMBED];
         hipLaunchKernelGGL(tp_wait_token_kernel, dim3(1), dim3(1), 0, st, (const TPMail*)g->mail[k], g->seq[k], s->st);
-        hipLaunchKernelGGL(embed_kernel, dim3(1), dim3(256), 0, st, (const void*)emb.data, (const float*)emb.scales, emb.dtype,
-                           (const DecodeState*)s->st, E, s->x);
+        launch_embed(emb, s->st, E, s->x, st);
     }
     // the o-proj / down GEMVs push their partial rows and raise the flags themselves (EPI_TP) where a kernel for it exists;
     // otherwise (grid == 0: BF16 model, first-generation strict kernels) a scatter launch follows the GEMV
@@ -610,16 +702,15 @@ int jh_tp_group_decode_n(jh_tp_group* g, int32_t first_token, int start_pos, int
             const JWeight& emb = s->m->global_w[JH_W_EMBED];
             HIPCHK(hipSetDevice(s->m->device));
             if (k == 0) {
-                hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, s->stream, s->st, start_pos, first_token, 0);
-                hipLaunchKernelGGL(embed_kernel, dim3(1), dim3(256), 0, s->stream, (const void*)emb.data, (const float*)emb.scales, emb.dtype,
-                                   (const DecodeState*)s->st, E, s->x);
+                launch_set_state(s->st, start_pos, first_token, s->stream);
+                launch_embed(emb, s->st, E, s->x, s->stream);
             } else {
                 // the first row reaches the other shards through their mailbox, like every later one: seq = this shard's counter
                 unsigned cur = 0;
                 HIPCHK(hipMemcpy(&cur, g->seq[k], sizeof(cur), hipMemcpyDeviceToHost));
                 TPMail m0{first_token, start_pos, cur, 0};
                 HIPCHK(hipMemcpy(g->mail[k], &m0, sizeof(m0), hipMemcpyHostToDevice));
-                hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, s->stream, s->st, start_pos, first_token, 0);
+                launch_set_state(s->st, start_pos, first_token, s->stream);
             }
             HIPCHK(hipGetLastError());
         }
@@ -672,9 +763,8 @@ int jh_tp_group_decode_n(jh_tp_group* g, int32_t first_token, int start_pos, int
         jh_session* s = g->sh[k];
         const JWeight& emb = s->m->global_w[JH_W_EMBED];
         HIPCHK(hipSetDevice(s->m->device));
-        hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, s->stream, s->st, start_pos, first_token, 0);
-        hipLaunchKernelGGL(embed_kernel, dim3(1), dim3(256), 0, s->stream, (const void*)emb.data, (const float*)emb.scales, emb.dtype,
-                           (const DecodeState*)s->st, E, s->x);
+        launch_set_state(s->st, start_pos, first_token, s->stream);
+        launch_embed(emb, s->st, E, s->x, s->stream);
         HIPCHK(hipGetLastError());
     }
     for (int i = 0; i < n; i++) {
@@ -692,9 +782,8 @@ int jh_tp_group_decode_n(jh_tp_group* g, int32_t first_token, int start_pos, int
             HIPCHK(hipSetDevice(s->m->device));
             HIPCHK(hipStreamWaitEvent(s->stream, g->evTok[0], 0));
             HIPCHK(hipMemcpyPeerAsync(&s->st->token, s->m->device, &s0->st->token, s0->m->device, sizeof(int), s->stream));
-            hipLaunchKernelGGL(set_pos_kernel, dim3(1), dim3(1), 0, s->stream, s->st, pos + 1);
-            hipLaunchKernelGGL(embed_kernel, dim3(1), dim3(256), 0, s->stream, (const void*)emb.data, (const float*)emb.scales, emb.dtype,
-                               (const DecodeState*)s->st, E, s->x);
+            launch_set_pos(s->st, pos + 1, s->stream);
+            launch_embed(emb, s->st, E, s->x, s->stream);
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventRecord(g->evTok[k], s->stream));
         }
@@ -820,10 +909,9 @@ int jh_tp_rank_decode_n(jh_tp_group* g, int32_t first_token, int start_pos, int 
     HIPCHK(hipStreamSynchronize(s->stream));
     const JWeight& emb = s->m->global_w[JH_W_EMBED];
     const int E = s->m->c.embedding_length;
-    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, s->stream, s->st, start_pos, first_token, 0);
+    launch_set_state(s->st, start_pos, first_token, s->stream);
     if (k == 0) {
-        hipLaunchKernelGGL(embed_kernel, dim3(1), dim3(256), 0, s->stream, (const void*)emb.data, (const float*)emb.scales, emb.dtype,
-                           (const DecodeState*)s->st, E, s->x);
+        launch_embed(emb, s->st, E, s->x, s->stream);
     } else {
         unsigned cur = 0;
         HIPCHK(hipMemcpy(&cur, g->seq[k], sizeof(cur), hipMemcpyDeviceToHost));

@@ -46,6 +46,30 @@ def test_only_c_abi_symbols_are_exported():
     assert set(jh) == set(_declared())
 
 
+def test_no_header_defines_a_static_kernel():
+    """A static __global__ function in a shared header is compiled into every translation unit that includes it, launched there or
+    not: each non-template kernel is defined once, in the .hip file that owns it (templates and __device__ helpers stay in headers)."""
+    csrc = os.path.join(ROOT, "jlama_amd", "csrc")
+    bad = []
+    for fn in sorted(os.listdir(csrc)):
+        if fn.endswith(".h"):
+            for i, line in enumerate(open(os.path.join(csrc, fn)), 1):
+                code = line.split("//")[0]
+                if re.search(r"\b__global__\b", code) and re.search(r"\bstatic\b", code):
+                    bad.append(f"{fn}:{i}")
+    assert not bad, bad
+
+
+def test_build_refreshes_a_stale_host_library():
+    """build() checks libjlamahost.so against its own key even when libjlamahip.so is current: an edit to host_mirror.cpp alone
+    must not leave the old host library in place."""
+    from jlama_amd import _native as N
+    with open(N.HOST_LIB_PATH + ".key", "w") as f:
+        f.write("0" * 32)
+    N.build()
+    assert open(N.HOST_LIB_PATH + ".key").read() == N.host_source_hash()
+
+
 def test_fails_loudly_without_gpu_or_library(monkeypatch):
     from jlama_amd import _native as N
     L = N.lib()
